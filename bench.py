@@ -9,6 +9,12 @@ outer RCCL syncs fire at their natural cadence (every H inner steps, counted
 across warmup + timed region) so a run with steps >= H measures them in-line.
 A separately-timed outer sync is always reported (outer_sync_ms, bytes) so
 short runs still quantify the sync cost. Rank 0 prints ONE JSON line.
+
+A plain run does only that: set up, warm up, time K steps, print the line.
+--dump-outputs DIR additionally saves the last timed step's results (loss.npy,
+params.npy) so two builds can be compared output for output; model init and
+data are seeded, so the same arguments give the same inputs on every run.
+--full is where measurements that need runs of their own belong.
 """
 
 from __future__ import annotations
@@ -34,6 +40,31 @@ if os.path.exists(_TUNED) and "PYTORCH_TUNABLEOP_ENABLED" not in os.environ:
 
 import torch
 
+# --dump-outputs: elements of the flat parameter buffer kept when it is larger
+_DUMP_SAMPLE = 1 << 22  # 4 Mi float32 = 16 MiB on disk
+
+
+def dump_outputs(out_dir: str, worker, flat: torch.Tensor) -> None:
+    """Write what a caller of the timed path holds after the last timed step:
+    the loss train_step() returned and the parameters it updated in place.
+    Parameters are read from the flat working buffer the model's tensors
+    alias; a buffer over _DUMP_SAMPLE elements is reduced to a fixed, seeded
+    index sample (same indices for the same model on every run)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            np.asarray([worker.last_loss], dtype=np.float64))
+    n = flat.numel()
+    if n > _DUMP_SAMPLE:
+        g = torch.Generator(device="cpu").manual_seed(20240229)
+        idx = torch.randint(0, n, (_DUMP_SAMPLE,), generator=g).sort().values
+        vals = flat[idx.to(flat.device)]
+    else:
+        vals = flat
+    np.save(os.path.join(out_dir, "params.npy"),
+            vals.detach().float().cpu().numpy())
+
 
 def main() -> int:
     p = argparse.ArgumentParser()
@@ -57,6 +88,14 @@ def main() -> int:
     p.add_argument("--memory-mode", default="full", choices=("full", "lean"),
                    help="lean: bf16-SR master-free params, 8-bit state, streamed "
                         "grads, host theta0 (configs 4/5 sizing)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step "
+                        "produced (loss + a fixed seeded sample of the updated "
+                        "parameters) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements that need runs of "
+                        "their own (none at present: every figure in the result "
+                        "line is a by-product of the plain run)")
     args = p.parse_args()
 
     from hypha_amd import models, ops
@@ -172,6 +211,9 @@ def main() -> int:
                    if args.memory_mode == "lean" else worker.fp.numel)
     payload_bytes_per_sync = model_numel * 2  # bf16 comm dtype
     synced_in_window = worker.round - rounds_before
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, worker,
+                     worker.flat if args.memory_mode == "lean" else worker.fp.flat)
     if rank == 0:
         result = {
             "metric": "tokens/sec (node) + outer-sync bytes, Llama-3-8B DiLoCo H=100 at 1/2/4/8 GPUs",

@@ -26,6 +26,12 @@ def free_port():
     return p
 
 
+@pytest.fixture
+def tmp_path(short_tmp_path):
+    # the workers bind <work-root>/hypha-<job>/bridge.sock: keep it < 108 bytes
+    return short_tmp_path
+
+
 @pytest.fixture(scope="module")
 def binaries():
     if not (BIN / "hypha-gateway").exists():

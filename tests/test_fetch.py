@@ -32,6 +32,12 @@ def free_port():
     return p
 
 
+@pytest.fixture
+def tmp_path(short_tmp_path):
+    # the workers bind <work-root>/hypha-<job>/bridge.sock: keep it < 108 bytes
+    return short_tmp_path
+
+
 @pytest.fixture()
 def http_root(tmp_path):
     root = tmp_path / "www"

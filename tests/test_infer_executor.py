@@ -20,6 +20,12 @@ class UDSHttpServer(socketserver.ThreadingUnixStreamServer):
     daemon_threads = True
 
 
+@pytest.fixture
+def tmp_path(short_tmp_path):
+    # bridge.sock is bound inside it: a Unix socket path holds < 108 bytes
+    return short_tmp_path
+
+
 def test_infer_executor_end_to_end(tmp_path):
     from safetensors.torch import load_file
 
