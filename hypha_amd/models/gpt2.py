@@ -69,7 +69,8 @@ class GPT2Block(nn.Module):
             x = x + self.attn_out(o.transpose(1, 2).reshape(b, s, h))
         else:
             # serving: append into the pre-allocated bshd cache; decode via
-            # the flash-decoding kernel, prefill via the MFMA flash kernel
+            # the flash-decoding kernel, an aligned first pass via the MFMA
+            # flash kernel, ragged / chunked prefill via ops.attn_prefill
             q = q.view(b, s, self.n_heads, hd)
             k = k.view(b, s, self.n_heads, hd)
             v = v.view(b, s, self.n_heads, hd)
@@ -81,16 +82,9 @@ class GPT2Block(nn.Module):
             elif pos == 0 and (not x.is_cuda or s % 128 == 0):
                 o = ops.flash_attention(q, k, v, causal=True, layout="bshd")
                 o = o.reshape(b, s, h)
-            else:  # ragged prefill / chunked continuation (fp32 reference)
-                kd, vd = cache.dequant(t)
-                kh = kd.transpose(1, 2)
-                vh = vd.transpose(1, 2)
-                qh = q.transpose(1, 2)
-                scores = (qh.float() @ kh.float().transpose(-1, -2)) / math.sqrt(hd)
-                mask = torch.arange(t, device=x.device)[None, :] > (
-                    pos + torch.arange(s, device=x.device)[:, None])
-                p = torch.softmax(scores.masked_fill(mask, float("-inf")), dim=-1)
-                o = (p @ vh.float()).to(x.dtype).transpose(1, 2).reshape(b, s, h)
+            else:  # ragged prefill / chunked continuation over the cache
+                o = ops.attn_prefill(q, cache.k, cache.v, pos, cache.k_scale,
+                                     cache.v_scale).reshape(b, s, h)
             x = x + self.attn_out(o)
         x = x + self.mlp_proj(ops.gelu(self.mlp_fc(self.ln2(x))))
         return x
@@ -130,13 +124,17 @@ class GPT2ForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
                  temperature: float = 0.0, top_k: int = 0,
-                 seed: int | None = None) -> torch.Tensor:
-        """KV-cache decoding (prefill once, then one token per step via the
+                 seed: int | None = None,
+                 prefill_chunk: int | None = None) -> torch.Tensor:
+        """KV-cache decoding (prefill, then one token per step via the
         flash-decoding kernel); same sampling surface as the Llama family so
         inference jobs can run any registry model. Sequences are capped at
-        n_positions (absolute position embeddings)."""
+        n_positions (absolute position embeddings). prefill_chunk feeds the
+        prompt in pieces of at most that many tokens; None = one pass."""
         from .kv_cache import KVCache
 
+        if prefill_chunk is not None and prefill_chunk < 1:
+            raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
         self.eval()
         b, s = input_ids.shape
         max_len = min(s + max_new_tokens, self.cfg.n_positions)
@@ -150,13 +148,25 @@ class GPT2ForCausalLM(nn.Module):
         tokens = input_ids
         x_in = input_ids
         pos = 0
+
+        def run_blocks(ids, pos):
+            idx = torch.arange(pos, pos + ids.shape[1], device=ids.device)
+            x = self.wte(ids) + self.wpe(idx)
+            for blk, cache in zip(self.blocks, caches):
+                x = blk(x, cache=cache, pos=pos)
+            return x
+
+        # chunked prefill: all pieces but the last only fill the caches
+        while (prefill_chunk is not None and max_new_tokens > 0
+               and x_in.shape[1] > prefill_chunk
+               and pos + x_in.shape[1] <= self.cfg.n_positions):
+            run_blocks(x_in[:, :prefill_chunk], pos)
+            pos += prefill_chunk
+            x_in = x_in[:, prefill_chunk:]
         for _ in range(max_new_tokens):
             if pos + x_in.shape[1] > self.cfg.n_positions:
                 break  # absolute-position ceiling reached
-            idx = torch.arange(pos, pos + x_in.shape[1], device=x_in.device)
-            x = self.wte(x_in) + self.wpe(idx)
-            for blk, cache in zip(self.blocks, caches):
-                x = blk(x, cache=cache, pos=pos)
+            x = run_blocks(x_in, pos)
             x = self.ln_f(x[:, -1:])
             logits = F.linear(x, self.wte.weight)[:, 0]
             if temperature <= 0:

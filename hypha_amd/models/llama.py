@@ -102,8 +102,9 @@ class Attention(nn.Module):
             return self.wo(o.reshape(b, s, -1))
         # inference with KV cache: rotate at absolute positions, append into
         # the pre-allocated bshd cache, then attend over the valid prefix.
-        # Decode (s==1) runs the native flash-decoding kernel; prefill runs
-        # the MFMA flash kernel; chunked continuation falls back to fp32.
+        # Decode (s==1) runs the native flash-decoding kernel; an aligned
+        # first pass runs the MFMA flash kernel; ragged prompts and chunked
+        # continuation run the cache-reading prefill kernel (ops.attn_prefill).
         q, k = ops.apply_rope_qk(q, k, cos[pos:], sin[pos:], layout="bshd")
         t = cache.append(k, v)
         if s == 1:
@@ -113,19 +114,9 @@ class Attention(nn.Module):
         if pos == 0 and (not x.is_cuda or s % 128 == 0):
             o = ops.flash_attention(q, k, v, causal=True, layout="bshd")
             return self.wo(o.reshape(b, s, -1))
-        # chunked prefill with a position offset (rare path; fp32 reference)
-        kc, vc = cache.dequant(t)
-        rep = cfg.n_heads // cfg.n_kv_heads
-        qh = q.transpose(1, 2)  # [b, hq, s, d]
-        kh = kc.transpose(1, 2).repeat_interleave(rep, dim=1)
-        vh = vc.transpose(1, 2).repeat_interleave(rep, dim=1)
-        scores = (qh.float() @ kh.float().transpose(-1, -2)) / math.sqrt(hd)
-        mask = torch.arange(t, device=x.device)[None, :] > (
-            pos + torch.arange(s, device=x.device)[:, None]
-        )
-        scores = scores.masked_fill(mask, float("-inf"))
-        p = torch.softmax(scores, dim=-1)
-        o = (p @ vh.float()).to(x.dtype).transpose(1, 2)
+        # ragged prompt or chunked continuation: attend over the cache
+        o = ops.attn_prefill(q, cache.k, cache.v, pos, cache.k_scale,
+                             cache.v_scale)
         return self.wo(o.reshape(b, s, -1))
 
 
@@ -223,11 +214,16 @@ class LlamaForCausalLM(nn.Module):
 @torch.no_grad()
 def _generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
               temperature: float = 0.0, top_k: int = 0,
-              seed: int | None = None, kv_quant: str | None = None) -> torch.Tensor:
+              seed: int | None = None, kv_quant: str | None = None,
+              prefill_chunk: int | None = None) -> torch.Tensor:
     """Autoregressive generation with a per-layer KV cache (inference parity:
-    the reference serves inference through the same executor surface)."""
+    the reference serves inference through the same executor surface).
+    prefill_chunk feeds the prompt in pieces of at most that many tokens
+    (activation memory bounded by the chunk); None prefills in one pass."""
     from .kv_cache import KVCache
 
+    if prefill_chunk is not None and prefill_chunk < 1:
+        raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
     self.eval()
     b, s = input_ids.shape
     max_len = s + max_new_tokens
@@ -241,10 +237,22 @@ def _generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
     tokens = input_ids
     x_in = input_ids
     pos = 0
-    for _ in range(max_new_tokens):
-        x = self.embed(x_in)
+
+    def run_blocks(ids, pos):
+        x = self.embed(ids)
         for blk, cache in zip(self.blocks, caches):
             x = blk(x, self.rope_cos, self.rope_sin, cache=cache, pos=pos)
+        return x
+
+    # chunked prefill: all pieces but the last only fill the caches; the
+    # last piece goes through the loop below and feeds the sampler
+    while (prefill_chunk is not None and max_new_tokens > 0
+           and x_in.shape[1] > prefill_chunk):
+        run_blocks(x_in[:, :prefill_chunk], pos)
+        pos += prefill_chunk
+        x_in = x_in[:, prefill_chunk:]
+    for _ in range(max_new_tokens):
+        x = run_blocks(x_in, pos)
         x = self.norm(x[:, -1:])
         if self.lm_head is not None:
             logits = self.lm_head(x)[:, 0]

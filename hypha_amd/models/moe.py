@@ -358,12 +358,16 @@ class MoEForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
                  temperature: float = 0.0, top_k: int = 0,
-                 seed: int | None = None) -> torch.Tensor:
-        """KV-cache decoding (prefill once, then one token per step via the
+                 seed: int | None = None,
+                 prefill_chunk: int | None = None) -> torch.Tensor:
+        """KV-cache decoding (prefill, then one token per step via the
         flash-decoding kernel; same sampling surface as the Llama family so
-        inference jobs can run any registry model)."""
+        inference jobs can run any registry model). prefill_chunk feeds the
+        prompt in pieces of at most that many tokens; None = one pass."""
         from .kv_cache import KVCache
 
+        if prefill_chunk is not None and prefill_chunk < 1:
+            raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
         self.eval()
         b, s = input_ids.shape
         dtype = self.embed.weight.dtype
@@ -376,10 +380,21 @@ class MoEForCausalLM(nn.Module):
         tokens = input_ids
         x_in = input_ids
         pos = 0
-        for _ in range(max_new_tokens):
-            x = self.embed(x_in)
+
+        def run_blocks(ids, pos):
+            x = self.embed(ids)
             for blk, cache in zip(self.blocks, caches):
                 x, _ = blk(x, self.rope_cos, self.rope_sin, cache=cache, pos=pos)
+            return x
+
+        # chunked prefill: all pieces but the last only fill the caches
+        while (prefill_chunk is not None and max_new_tokens > 0
+               and x_in.shape[1] > prefill_chunk):
+            run_blocks(x_in[:, :prefill_chunk], pos)
+            pos += prefill_chunk
+            x_in = x_in[:, prefill_chunk:]
+        for _ in range(max_new_tokens):
+            x = run_blocks(x_in, pos)
             x = self.norm(x[:, -1:])
             logits = self.lm_head(x)[:, 0]
             if temperature <= 0:

@@ -55,6 +55,7 @@ from .interface import (  # noqa: E402
     add_rmsnorm,
     apply_rope_qk,
     attn_decode,
+    attn_prefill,
     cross_entropy_loss,
     extract_delta,
     flash_attention,
@@ -78,6 +79,7 @@ __all__ = [
     "add_rmsnorm",
     "apply_rope_qk",
     "attn_decode",
+    "attn_prefill",
     "swiglu",
     "flash_attention",
     "cross_entropy_loss",

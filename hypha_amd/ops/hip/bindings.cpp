@@ -104,6 +104,12 @@ torch::Tensor attn_decode_fp8_graph(torch::Tensor q, torch::Tensor kcache,
 void kv_append_fp8_(torch::Tensor k, torch::Tensor v, torch::Tensor k8,
                     torch::Tensor v8, torch::Tensor kscale, torch::Tensor vscale,
                     torch::Tensor pos);
+// prefill.hip (ragged / chunked prefill attention over the KV cache)
+torch::Tensor attn_prefill(torch::Tensor q, torch::Tensor kcache, torch::Tensor vcache,
+                           long pos);
+torch::Tensor attn_prefill_fp8(torch::Tensor q, torch::Tensor kcache,
+                               torch::Tensor vcache, torch::Tensor kscale,
+                               torch::Tensor vscale, long pos);
 // skinny_gemm.hip (decode GEMV, M <= 8)
 torch::Tensor skinny_gemm(torch::Tensor x, torch::Tensor w);
 
@@ -152,5 +158,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_fp8", &attn_decode_fp8);
   m.def("attn_decode_fp8_graph", &attn_decode_fp8_graph);
   m.def("kv_append_fp8_", &kv_append_fp8_);
+  m.def("attn_prefill", &attn_prefill);
+  m.def("attn_prefill_fp8", &attn_prefill_fp8);
   m.def("skinny_gemm", &skinny_gemm);
 }

@@ -1,0 +1,363 @@
+// Prefill attention over the KV cache for CDNA4 (gfx950): ragged prompts
+// (any s >= 1) and chunked continuation (pos > 0), bf16 or fp8-e4m3 cache.
+//
+// Problem shape: q [B, s, Hq, D] bf16 (bshd) holds the chunk's queries, q
+// row i sitting at absolute position pos + i. The chunk's own K/V rows are
+// already appended, so the cache [B, T_alloc, Hkv, D] (bshd, read in place —
+// the layout KVCache and decode.hip use) is valid for t = pos + s rows.
+// kv index j is visible to q row i iff j <= pos + i.
+//
+// The MFMA structure is attn_fwd_kernel's (attention.hip; fragment maps are
+// documented there and verified by probe.hip): one workgroup = 4 waves x 32
+// q rows, KV tile 64, swapped QK^T (lane-local softmax state), O accumulated
+// transposed, in-register P pack, XOR-16 swizzled K tile, V transposed at
+// staging, register prefetch of the next tile. What differs:
+//  * the causal diagonal is shifted by pos; the per-workgroup kv bound is
+//    min(t, pos + q0wg + 128);
+//  * q rows >= s load zeros and are never stored (in bshd the row after the
+//    last one belongs to the next batch);
+//  * kv rows >= the workgroup bound are STAGED AS ZEROS, never loaded: no
+//    read past T_alloc, and no stale or non-finite cache tail (a masked
+//    p = 0 times a NaN V would still poison O);
+//  * QUANT=true dequantizes e4m3 rows (per-row fp32 scale) while writing the
+//    LDS images, as decode.hip does, so the MFMA phases are shared.
+// No lse, no backward. Grid (ceil(s/128), B*Hq): a short chunk against a
+// long prefix runs few workgroups (no split-KV).
+
+#include <torch/extension.h>
+
+#include "attn_tile.h"
+#include "hip_common.h"
+
+namespace {
+
+// 8 e4m3 bytes * row scale -> 8 bf16 (fp32 multiply, RNE: the same values
+// KVCache.dequant produces)
+__device__ __forceinline__ s16x8 dequant8(uint2 raw, float sc) {
+  s16x8 o;
+  o[0] = f2bf(__builtin_amdgcn_cvt_f32_fp8(raw.x, 0) * sc);
+  o[1] = f2bf(__builtin_amdgcn_cvt_f32_fp8(raw.x, 1) * sc);
+  o[2] = f2bf(__builtin_amdgcn_cvt_f32_fp8(raw.x, 2) * sc);
+  o[3] = f2bf(__builtin_amdgcn_cvt_f32_fp8(raw.x, 3) * sc);
+  o[4] = f2bf(__builtin_amdgcn_cvt_f32_fp8(raw.y, 0) * sc);
+  o[5] = f2bf(__builtin_amdgcn_cvt_f32_fp8(raw.y, 1) * sc);
+  o[6] = f2bf(__builtin_amdgcn_cvt_f32_fp8(raw.y, 2) * sc);
+  o[7] = f2bf(__builtin_amdgcn_cvt_f32_fp8(raw.y, 3) * sc);
+  return o;
+}
+
+template <int HD, bool QUANT>
+__global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
+    const short* __restrict__ qg, const void* __restrict__ kgv,
+    const void* __restrict__ vgv, const float* __restrict__ kscale,
+    const float* __restrict__ vscale, short* __restrict__ og, int Hq, int Hkv,
+    int s, int pos, int T_alloc, float scale) {
+  constexpr int KC = HD / 16;        // 16-wide k chunks over head dim
+  constexpr int DBLK = HD / 32;      // 32-row d blocks
+  constexpr int VT_PITCH = KVB + PADV;
+  __shared__ __attribute__((aligned(16))) short k_lds[KVB * HD];
+  __shared__ __attribute__((aligned(16))) short vt_lds[HD * VT_PITCH];
+  __shared__ __attribute__((aligned(16))) short ot_lds[NWAVE][QB * (HD + 8)];  // epilogue transpose
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int hi = lane >> 5;  // half-wave
+  const int ln = lane & 31;
+
+  const int bh = blockIdx.y;
+  const int b = bh / Hq;
+  const int hq = bh % Hq;
+  const int hkv = hq / (Hq / Hkv);
+  const int t = pos + s;  // valid cache rows
+  const long long q_ss = (long long)Hq * HD;
+  const long long qbase = (long long)b * s * q_ss + (long long)hq * HD;
+  const long long kvrow0 = (long long)b * T_alloc;  // cache row index of kv 0
+
+  const int q0wg = blockIdx.x * WGQ;
+  const int q0 = q0wg + wid * QB;   // this wave's q rows
+  const int qrow = q0 + ln;         // this lane's q row (its S^T column)
+  const bool wave_live = q0 < s;    // a wave past the ragged tail only stages
+  // last kv index this lane's row may see; rows >= s (never stored) are
+  // clamped to the valid prefix so their state stays finite too
+  const int vis = min(pos + qrow, t - 1);
+  // exclusive kv bound of this workgroup: >= 1, <= t <= T_alloc
+  const int kv_end = min(t, pos + q0wg + WGQ);
+
+  // ---- Q fragments: B operand of S^T = mfma(K, Q); lane ln = q column ----
+  s16x8 qfrag[KC];
+#pragma unroll
+  for (int kc = 0; kc < KC; ++kc) {
+    s16x8 qv = {};
+    if (qrow < s)
+      qv = *reinterpret_cast<const s16x8*>(qg + qbase + (long long)qrow * q_ss +
+                                           16 * kc + 8 * hi);
+    qfrag[kc] = qv;
+  }
+
+  f32x16 ot[DBLK] = {};
+  float m_run = -INFINITY, l_run = 0.f;
+
+  // ---- register-staged K/V prefetch: the next tile's global loads are
+  // issued before the current tile's MFMA phase. fp8 mode keeps the raw
+  // bytes + row scale in registers and converts at the LDS write, so the
+  // conversion does not wait on the loads it was meant to hide ----
+  constexpr int KCH = KVB * HD / 8 / 256;  // 8-elem K chunks per thread
+  constexpr int VCH = HD / 32;             // 8-elem V chunks per thread
+  s16x8 kreg[KCH], vreg[VCH];              // bf16 mode
+  uint2 kraw[KCH], vraw[VCH];              // fp8 mode
+  float ksc[KCH], vsc = 0.f;
+  auto load_tile = [&](int kv0) {
+#pragma unroll
+    for (int c = 0; c < KCH; ++c) {
+      int cc = c * 256 + tid;
+      int row = cc / (HD / 8), e0 = (cc % (HD / 8)) * 8;
+      const bool ok = kv0 + row < kv_end;
+      const long long srow = (kvrow0 + kv0 + row) * Hkv + hkv;
+      if (QUANT) {
+        kraw[c] = make_uint2(0u, 0u);
+        ksc[c] = 0.f;
+        if (ok) {
+          kraw[c] = *reinterpret_cast<const uint2*>(
+              reinterpret_cast<const unsigned char*>(kgv) + srow * HD + e0);
+          ksc[c] = kscale[srow];
+        }
+      } else {
+        s16x8 kv8 = {};
+        if (ok)
+          kv8 = *reinterpret_cast<const s16x8*>(
+              reinterpret_cast<const short*>(kgv) + srow * HD + e0);
+        kreg[c] = kv8;
+      }
+    }
+    {
+      int kvr = tid & 63;
+      const bool ok = kv0 + kvr < kv_end;
+      const long long srow = (kvrow0 + kv0 + kvr) * Hkv + hkv;
+      if (QUANT) vsc = ok ? vscale[srow] : 0.f;
+#pragma unroll
+      for (int i = 0; i < VCH; ++i) {
+        int e0 = (i * 4 + (tid >> 6)) * 8;
+        if (QUANT) {
+          vraw[i] = make_uint2(0u, 0u);
+          if (ok)
+            vraw[i] = *reinterpret_cast<const uint2*>(
+                reinterpret_cast<const unsigned char*>(vgv) + srow * HD + e0);
+        } else {
+          s16x8 v8 = {};
+          if (ok)
+            v8 = *reinterpret_cast<const s16x8*>(
+                reinterpret_cast<const short*>(vgv) + srow * HD + e0);
+          vreg[i] = v8;
+        }
+      }
+    }
+  };
+  auto write_tile = [&]() {
+#pragma unroll
+    for (int c = 0; c < KCH; ++c) {
+      int cc = c * 256 + tid;
+      int row = cc / (HD / 8), e0 = (cc % (HD / 8)) * 8;
+      s16x8 k8 = QUANT ? dequant8(kraw[c], ksc[c]) : kreg[c];
+      *reinterpret_cast<s16x8*>((char*)k_lds + k_lds_off<HD>(row, e0)) = k8;
+    }
+    // V^T transpose: lane-per-kv stores walk the contiguous image row
+#pragma unroll
+    for (int i = 0; i < VCH; ++i) {
+      int kvr = tid & 63;
+      int e0 = (i * 4 + (tid >> 6)) * 8;
+      s16x8 v8 = QUANT ? dequant8(vraw[i], vsc) : vreg[i];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) vt_lds[(e0 + j) * VT_PITCH + kvr] = v8[j];
+    }
+  };
+
+  load_tile(0);
+  for (int kv0 = 0; kv0 < kv_end; kv0 += KVB) {
+    __syncthreads();  // previous tile's LDS consumers done
+    write_tile();
+    if (kv0 + KVB < kv_end) load_tile(kv0 + KVB);  // prefetch next tile
+    __syncthreads();  // this tile's LDS image ready
+
+    // wave fully above the shifted diagonal, or fully past the q tail.
+    // Tile 0 is never skipped for a live wave (0 <= pos + q0 + 31).
+    if (!wave_live || kv0 > pos + q0 + QB - 1) continue;
+
+    // ---- S^T = K Q^T : two 32-kv accumulators ----
+    f32x16 st[2];
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb) {
+      f32x16 acc = {};
+#pragma unroll
+      for (int kc = 0; kc < KC; ++kc) {
+        s16x8 kf = *reinterpret_cast<const s16x8*>(
+            (char*)k_lds + k_lds_off<HD>(32 * mb + ln, 16 * kc + 8 * hi));
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qfrag[kc], acc, 0, 0, 0);
+      }
+      st[mb] = acc;
+    }
+
+    // ---- online softmax over the 32 regs (all kv of this tile, own q) ----
+    float tmax = -INFINITY;
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        int kv = kv0 + 32 * mb + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        float sc = st[mb][r] * scale;
+        if (kv > vis) sc = -INFINITY;
+        st[mb][r] = sc;
+        tmax = fmaxf(tmax, sc);
+      }
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    // kv 0 is visible to every row (vis >= 0) and sits in tile 0, which no
+    // live wave skips: m_new is finite from the first processed tile on, so
+    // exp(m_run - m_new) is exp(-inf) = 0 there and never exp(-inf + inf);
+    // a later tile that is fully masked for a row leaves m_new = m_run.
+    const float m_new = fmaxf(m_run, tmax);
+    const float alpha = __expf(m_run - m_new);
+    float psum = 0.f;
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float p = __expf(st[mb][r] - m_new);
+        st[mb][r] = p;
+        psum += p;
+      }
+    psum += __shfl_xor(psum, 32, 64);
+    l_run = l_run * alpha + psum;
+    m_run = m_new;
+#pragma unroll
+    for (int db = 0; db < DBLK; ++db)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) ot[db][r] *= alpha;
+
+    // ---- pack P^T to bf16 B-fragments (pair-pack + half swap) ----
+    s16x8 pfrag[4];
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb) {
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        unsigned c0 = pack_bf16x2(st[mb][8 * half + 0], st[mb][8 * half + 1]);
+        unsigned c1 = pack_bf16x2(st[mb][8 * half + 2], st[mb][8 * half + 3]);
+        unsigned c2 = pack_bf16x2(st[mb][8 * half + 4], st[mb][8 * half + 5]);
+        unsigned c3 = pack_bf16x2(st[mb][8 * half + 6], st[mb][8 * half + 7]);
+        auto r02 = __builtin_amdgcn_permlane32_swap(c0, c2, false, false);
+        auto r13 = __builtin_amdgcn_permlane32_swap(c1, c3, false, false);
+        unsigned frag[4] = {(unsigned)r02[0], (unsigned)r13[0], (unsigned)r02[1],
+                            (unsigned)r13[1]};
+        pfrag[2 * mb + half] = *reinterpret_cast<s16x8*>(frag);
+      }
+    }
+
+    // ---- O^T += V^T P^T ----
+#pragma unroll
+    for (int db = 0; db < DBLK; ++db) {
+#pragma unroll
+      for (int kc = 0; kc < 4; ++kc) {
+        s16x8 vf = *reinterpret_cast<const s16x8*>(
+            vt_lds + (32 * db + ln) * VT_PITCH + 16 * kc + 8 * hi);
+        ot[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pfrag[kc], ot[db], 0, 0, 0);
+      }
+    }
+  }
+
+  if (!wave_live) return;  // no barrier below this point
+
+  // ---- epilogue: normalize, transpose through LDS, coalesced store of the
+  // rows < s only ----
+  const float inv_l = l_run > 0.f ? 1.f / l_run : 0.f;
+  constexpr int OPITCH = HD + 8;
+#pragma unroll
+  for (int db = 0; db < DBLK; ++db)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      int d = 32 * db + (r & 3) + 8 * (r >> 2) + 4 * hi;
+      ot_lds[wid][ln * OPITCH + d] = f2bf(ot[db][r] * inv_l);
+    }
+  __builtin_amdgcn_s_waitcnt(0);  // lgkmcnt(0): own-wave LDS writes visible
+#pragma unroll
+  for (int it = 0; it < QB * HD / 8 / 64; ++it) {
+    int c = it * 64 + lane;
+    int row = c / (HD / 8), e0 = (c % (HD / 8)) * 8;
+    if (q0 + row < s) {
+      s16x8 o8 = *reinterpret_cast<const s16x8*>(ot_lds[wid] + row * OPITCH + e0);
+      *reinterpret_cast<s16x8*>(og + qbase + (long long)(q0 + row) * q_ss + e0) = o8;
+    }
+  }
+}
+
+torch::Tensor attn_prefill_impl(torch::Tensor q, torch::Tensor kcache,
+                                torch::Tensor vcache, const torch::Tensor* kscale,
+                                const torch::Tensor* vscale, long pos) {
+  TORCH_CHECK(q.is_cuda() && kcache.is_cuda() && vcache.is_cuda(),
+              "prefill: tensors must be on the GPU");
+  TORCH_CHECK(q.dim() == 4 && q.dtype() == torch::kBFloat16 && q.is_contiguous(),
+              "prefill: q must be contiguous bf16 [B, s, Hq, D]");
+  TORCH_CHECK(kcache.dim() == 4 && kcache.is_contiguous() && vcache.is_contiguous() &&
+                  vcache.sizes() == kcache.sizes() && vcache.dtype() == kcache.dtype(),
+              "prefill: k/v caches must be contiguous [B, T_alloc, Hkv, D] of one dtype");
+  const bool quant = kcache.dtype() == torch::kFloat8_e4m3fn;
+  TORCH_CHECK(quant || kcache.dtype() == torch::kBFloat16,
+              "prefill: cache must be bf16 or float8_e4m3fn");
+  const long B = q.size(0), s = q.size(1), Hq = q.size(2), HD = q.size(3);
+  const long T_alloc = kcache.size(1), Hkv = kcache.size(2);
+  TORCH_CHECK(kcache.size(0) == B && kcache.size(3) == HD, "prefill: q/cache shape mismatch");
+  TORCH_CHECK(HD == 64 || HD == 128, "prefill: head dim must be 64 or 128");
+  TORCH_CHECK(Hkv >= 1 && Hq % Hkv == 0, "prefill: Hq must be a multiple of Hkv");
+  TORCH_CHECK(s >= 1 && pos >= 0 && pos + s <= T_alloc,
+              "prefill: pos + s exceeds the cache (pos=", pos, ", s=", s,
+              ", T_alloc=", T_alloc, ")");
+  TORCH_CHECK(B * Hq <= 65535 && T_alloc + WGQ < (1L << 31), "prefill: shape too large");
+  const float* ksp = nullptr;
+  const float* vsp = nullptr;
+  if (quant) {
+    TORCH_CHECK(kscale && vscale, "prefill: fp8 cache needs row scales");
+    for (const torch::Tensor* sc : {kscale, vscale})
+      TORCH_CHECK(sc->is_cuda() && sc->dtype() == torch::kFloat32 && sc->is_contiguous() &&
+                      sc->dim() == 3 && sc->size(0) == B && sc->size(1) == T_alloc &&
+                      sc->size(2) == Hkv,
+                  "prefill: scales must be contiguous fp32 [B, T_alloc, Hkv]");
+    ksp = kscale->data_ptr<float>();
+    vsp = vscale->data_ptr<float>();
+  }
+
+  auto o = torch::empty_like(q);
+  const float scale = 1.0f / sqrtf((float)HD);
+  dim3 grid((unsigned)((s + WGQ - 1) / WGQ), (unsigned)(B * Hq));
+  hipStream_t stream = hypha_stream();
+
+#define PREFILL_LAUNCH(HDV, QV)                                                       \
+  hipLaunchKernelGGL((attn_prefill_kernel<HDV, QV>), grid, dim3(256), 0, stream,      \
+                     (const short*)q.data_ptr(), (const void*)kcache.data_ptr(),      \
+                     (const void*)vcache.data_ptr(), ksp, vsp, (short*)o.data_ptr(),  \
+                     (int)Hq, (int)Hkv, (int)s, (int)pos, (int)T_alloc, scale)
+  if (HD == 128 && !quant)
+    PREFILL_LAUNCH(128, false);
+  else if (HD == 128)
+    PREFILL_LAUNCH(128, true);
+  else if (!quant)
+    PREFILL_LAUNCH(64, false);
+  else
+    PREFILL_LAUNCH(64, true);
+#undef PREFILL_LAUNCH
+  return o;
+}
+
+}  // namespace
+
+// q [B, s, Hq, D] bf16; caches [B, T_alloc, Hkv, D] bf16 (bshd, the chunk's
+// own rows already appended); pos = absolute position of q row 0.
+// Returns o [B, s, Hq, D] bf16.
+torch::Tensor attn_prefill(torch::Tensor q, torch::Tensor kcache, torch::Tensor vcache,
+                           long pos) {
+  return attn_prefill_impl(q, kcache, vcache, nullptr, nullptr, pos);
+}
+
+// fp8 (OCP e4m3) cache with per-row fp32 scales [B, T_alloc, Hkv].
+torch::Tensor attn_prefill_fp8(torch::Tensor q, torch::Tensor kcache,
+                               torch::Tensor vcache, torch::Tensor kscale,
+                               torch::Tensor vscale, long pos) {
+  return attn_prefill_impl(q, kcache, vcache, &kscale, &vscale, pos);
+}

@@ -10,6 +10,9 @@ The HIP extension ABI (hypha_amd._C):
   ce_bwd_(logits2d, targets, lse, scale) -> dlogits        # overwrites logits
   attn_fwd_ex(q, k, v, causal, layout) -> (o, lse)         # layout bhsd|bshd
   attn_bwd_ex(q, k, v, o, do, lse, causal, layout) -> (dq, dk, dv)
+  attn_decode(q, kcache, vcache, t) -> o                   # + _fp8 / _graph
+  attn_prefill(q, kcache, vcache, pos) -> o                # q bshd, any s >= 1
+  attn_prefill_fp8(q, kcache, vcache, kscale, vscale, pos) -> o
   adamw_step_(master, param, grad, m, v, lr, b1, b2, eps, wd, step)
   adamw8_step_(master, param, grad, m8, v8, m_scale, v_scale, ...)  # 8-bit state
   nesterov_step_(master, delta_bf16, momentum, lr, mu)
@@ -272,6 +275,46 @@ def attn_decode(q, kcache, vcache, t: int, kscale=None, vscale=None) -> torch.Te
     p = torch.softmax(scores, dim=-1)
     o = torch.einsum("bht,bhtd->bhd", p, vh)
     return o.to(q.dtype)
+
+
+# ---------------------------------------------------------------------------
+# KV-cache prefill attention (ragged prompts, chunked continuation)
+# ---------------------------------------------------------------------------
+
+
+def attn_prefill(q, kcache, vcache, pos: int, kscale=None, vscale=None) -> torch.Tensor:
+    """Multi-token attention of one prompt chunk over an appended KV cache.
+
+    q [B, s, Hq, D] (bshd), any s >= 1, row i at absolute position pos + i;
+    kcache/vcache [B, T_alloc, Hkv, D] bf16 OR fp8-e4m3 with per-row scales
+    [B, T_alloc, Hkv], already holding the chunk's own rows, so the valid
+    length is t = pos + s and kv j is visible to q row i iff j <= pos + i.
+    Returns [B, s, Hq, D] in q's dtype. Native MFMA kernel
+    (ops/hip/prefill.hip) on GPU for head dims 64/128; fp32 reference
+    otherwise. Inference only (no autograd).
+    """
+    s = q.shape[1]
+    t = pos + s
+    if pos < 0 or s < 1 or t > kcache.shape[1]:
+        raise ValueError(
+            f"attn_prefill: pos={pos}, s={s} do not fit a cache of "
+            f"{kcache.shape[1]} rows")
+    quant = kcache.dtype == torch.float8_e4m3fn
+    if quant and (kscale is None or vscale is None):
+        raise ValueError("attn_prefill: an fp8 cache needs kscale and vscale")
+    if (use_native(q) and q.shape[-1] in (64, 128)
+            and q.shape[2] % kcache.shape[2] == 0):
+        if quant:
+            return _c().attn_prefill_fp8(q.contiguous(), kcache, vcache, kscale,
+                                         vscale, pos)
+        return _c().attn_prefill(q.contiguous(), kcache, vcache, pos)
+    # reference path (CPU, or head dims the kernel doesn't cover)
+    if quant:
+        kc = (kcache[:, :t].float() * kscale[:, :t].unsqueeze(-1)).bfloat16()
+        vc = (vcache[:, :t].float() * vscale[:, :t].unsqueeze(-1)).bfloat16()
+    else:
+        kc, vc = kcache[:, :t], vcache[:, :t]
+    return reference.attention_cached(q, kc, vc, pos)
 
 
 def linear_skinny(x2d: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:

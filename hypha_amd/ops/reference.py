@@ -86,6 +86,31 @@ def attention(
     return torch.matmul(p, v.float()).to(q.dtype)
 
 
+def attention_cached(
+    q: torch.Tensor,  # [B, s, Hq, D]  chunk queries, row i at position pos + i
+    k: torch.Tensor,  # [B, t, Hkv, D] valid cache prefix, t = pos + s
+    v: torch.Tensor,  # [B, t, Hkv, D]
+    pos: int,
+) -> torch.Tensor:
+    """Prefill attention over a KV-cache prefix (bshd): kv index j is visible
+    to q row i iff j <= pos + i. fp32 math; returns [B, s, Hq, D] in q.dtype."""
+    s, hq, d = q.shape[1], q.shape[2], q.shape[3]
+    t = k.shape[1]
+    rep = hq // k.shape[2]
+    qh = q.transpose(1, 2)  # [B, Hq, s, D]
+    kh = k.transpose(1, 2)
+    vh = v.transpose(1, 2)
+    if rep != 1:
+        kh = kh.repeat_interleave(rep, dim=1)
+        vh = vh.repeat_interleave(rep, dim=1)
+    scores = (qh.float() @ kh.float().transpose(-1, -2)) / math.sqrt(d)
+    mask = torch.arange(t, device=q.device)[None, :] > (
+        pos + torch.arange(s, device=q.device)[:, None]
+    )
+    p = torch.softmax(scores.masked_fill(mask, float("-inf")), dim=-1)
+    return (p @ vh.float()).to(q.dtype).transpose(1, 2)
+
+
 # ---------------------------------------------------------------------------
 # SwiGLU MLP activation
 # ---------------------------------------------------------------------------

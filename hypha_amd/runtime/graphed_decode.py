@@ -97,17 +97,23 @@ class GraphedDecoder:
         self.step += 1
 
     @torch.no_grad()
-    def generate(self, input_ids: torch.Tensor, max_new_tokens: int) -> torch.Tensor:
+    def generate(self, input_ids: torch.Tensor, max_new_tokens: int,
+                 prefill_chunk: int | None = None) -> torch.Tensor:
         m = self.model
         b, s = input_ids.shape
         assert b == self.batch and max_new_tokens <= self.max_new
+        if prefill_chunk is not None and prefill_chunk < 1:
+            raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
         m.eval()
         for cache in self.caches:  # reuse across generate() calls
             cache.t = 0
-        # ---- prefill (eager, MFMA flash kernel) ----
-        x = m.embed(input_ids)
-        for blk, cache in zip(m.blocks, self.caches):
-            x = blk(x, m.rope_cos, m.rope_sin, cache=cache, pos=0)
+        # ---- prefill (eager; MFMA flash kernel for an aligned single pass,
+        # the cache-reading prefill kernel for ragged or chunked prompts) ----
+        step = s if prefill_chunk is None else prefill_chunk
+        for p0 in range(0, s, step):
+            x = m.embed(input_ids[:, p0:p0 + step])
+            for blk, cache in zip(m.blocks, self.caches):
+                x = blk(x, m.rope_cos, m.rope_sin, cache=cache, pos=p0)
         xl = m.norm(x[:, -1:])
         logits = (m.lm_head(xl) if m.lm_head is not None
                   else torch.nn.functional.linear(xl, m.embed.weight))

@@ -11,10 +11,13 @@ so the scheduler's FSM and lease machinery apply unchanged.
 
 Job config: {"model", "data": <fetch ref>, "results": <send ref>?,
              "max_new_tokens", "batch_size", "seq_len", "temperature",
-             "top_k", "num_batches", "kv_cache": "fp8"?}
+             "top_k", "num_batches", "kv_cache": "fp8"?,
+             "prefill_chunk": <int>?}
 
 Greedy Llama-family jobs on GPU decode through the hipGraph-captured step
-(runtime/graphed_decode.py); "kv_cache": "fp8" halves KV memory.
+(runtime/graphed_decode.py); "kv_cache": "fp8" halves KV memory;
+"prefill_chunk" feeds each prompt in pieces of at most that many tokens
+(activation memory bounded by the chunk; absent = one pass).
 """
 
 from __future__ import annotations
@@ -71,6 +74,11 @@ def main() -> int:
     num_batches = int(cfg.get("num_batches", 1))
     temperature = float(cfg.get("temperature", 0.0))
     top_k = int(cfg.get("top_k", 0))
+    prefill_chunk = cfg.get("prefill_chunk")
+    if prefill_chunk is not None:
+        prefill_chunk = int(prefill_chunk)
+        if prefill_chunk < 1:
+            raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
 
     # greedy Llama-family serving on GPU: hipGraph-captured decode step
     # (runtime/graphed_decode.py; eager decode is launch-bound)
@@ -95,11 +103,12 @@ def main() -> int:
                     break
                 prompts = ids[i : i + batch_size, :seq_len].to(device)
                 if graphed is not None and prompts.shape[0] == batch_size:
-                    out = graphed.generate(prompts, max_new_tokens=max_new)
+                    out = graphed.generate(prompts, max_new_tokens=max_new,
+                                           prefill_chunk=prefill_chunk)
                 else:
                     out = model.generate(prompts, max_new_tokens=max_new,
                                          temperature=temperature, top_k=top_k,
-                                         seed=0)
+                                         seed=0, prefill_chunk=prefill_chunk)
                 fname = f"completion-{out_idx:05d}.safetensors"
                 save_file({"tokens": out.cpu().contiguous()},
                           os.path.join(args.work_dir, fname))
