@@ -7,11 +7,9 @@
 // the layout KVCache and decode.hip use) is valid for t = pos + s rows.
 // kv index j is visible to q row i iff j <= pos + i.
 //
-// The MFMA structure is attn_fwd_kernel's (attention.hip; fragment maps are
-// documented there and verified by probe.hip): one workgroup = 4 waves x 32
-// q rows, KV tile 64, swapped QK^T (lane-local softmax state), O accumulated
-// transposed, in-register P pack, XOR-16 swizzled K tile, V transposed at
-// staging, register prefetch of the next tile. What differs:
+// The tile pipeline is attn_tile.h's, shared with attn_fwd_kernel
+// (attention.hip) and documented there; the fragment maps are verified by
+// probe.hip. What differs from attn_fwd_kernel:
 //  * the causal diagonal is shifted by pos; the per-workgroup kv bound is
 //    min(t, pos + q0wg + 128);
 //  * q rows >= s load zeros and are never stored (in bshd the row after the
@@ -54,7 +52,6 @@ __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
     int s, int pos, int T_alloc, float scale) {
   constexpr int KC = HD / 16;        // 16-wide k chunks over head dim
   constexpr int DBLK = HD / 32;      // 32-row d blocks
-  constexpr int VT_PITCH = KVB + PADV;
   __shared__ __attribute__((aligned(16))) short k_lds[KVB * HD];
   __shared__ __attribute__((aligned(16))) short vt_lds[HD * VT_PITCH];
   __shared__ __attribute__((aligned(16))) short ot_lds[NWAVE][QB * (HD + 8)];  // epilogue transpose
@@ -102,16 +99,14 @@ __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
   // issued before the current tile's MFMA phase. fp8 mode keeps the raw
   // bytes + row scale in registers and converts at the LDS write, so the
   // conversion does not wait on the loads it was meant to hide ----
-  constexpr int KCH = KVB * HD / 8 / 256;  // 8-elem K chunks per thread
-  constexpr int VCH = HD / 32;             // 8-elem V chunks per thread
-  s16x8 kreg[KCH], vreg[VCH];              // bf16 mode
-  uint2 kraw[KCH], vraw[VCH];              // fp8 mode
-  float ksc[KCH], vsc = 0.f;
+  constexpr int KCH = ATTN_KCH<HD>, VCH = ATTN_VCH<HD>;  // 8-elem chunks per thread
+  s16x8 kreg[KCH], vreg[VCH];  // bf16 chunks (fp8 mode: filled at the LDS write)
+  uint2 kraw[KCH], vraw[VCH];  // fp8 mode: raw bytes
+  float ksc[KCH], vsc = 0.f;   // fp8 mode: row scales
   auto load_tile = [&](int kv0) {
 #pragma unroll
     for (int c = 0; c < KCH; ++c) {
-      int cc = c * 256 + tid;
-      int row = cc / (HD / 8), e0 = (cc % (HD / 8)) * 8;
+      const int row = attn_k_row<HD>(c, tid), e0 = attn_k_e0<HD>(c, tid);
       const bool ok = kv0 + row < kv_end;
       const long long srow = (kvrow0 + kv0 + row) * Hkv + hkv;
       if (QUANT) {
@@ -131,13 +126,13 @@ __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
       }
     }
     {
-      int kvr = tid & 63;
+      const int kvr = attn_v_row(tid);
       const bool ok = kv0 + kvr < kv_end;
       const long long srow = (kvrow0 + kv0 + kvr) * Hkv + hkv;
       if (QUANT) vsc = ok ? vscale[srow] : 0.f;
 #pragma unroll
       for (int i = 0; i < VCH; ++i) {
-        int e0 = (i * 4 + (tid >> 6)) * 8;
+        const int e0 = attn_v_e0(i, tid);
         if (QUANT) {
           vraw[i] = make_uint2(0u, 0u);
           if (ok)
@@ -154,22 +149,13 @@ __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
     }
   };
   auto write_tile = [&]() {
+    if (QUANT) {
 #pragma unroll
-    for (int c = 0; c < KCH; ++c) {
-      int cc = c * 256 + tid;
-      int row = cc / (HD / 8), e0 = (cc % (HD / 8)) * 8;
-      s16x8 k8 = QUANT ? dequant8(kraw[c], ksc[c]) : kreg[c];
-      *reinterpret_cast<s16x8*>((char*)k_lds + k_lds_off<HD>(row, e0)) = k8;
+      for (int c = 0; c < KCH; ++c) kreg[c] = dequant8(kraw[c], ksc[c]);
+#pragma unroll
+      for (int i = 0; i < VCH; ++i) vreg[i] = dequant8(vraw[i], vsc);
     }
-    // V^T transpose: lane-per-kv stores walk the contiguous image row
-#pragma unroll
-    for (int i = 0; i < VCH; ++i) {
-      int kvr = tid & 63;
-      int e0 = (i * 4 + (tid >> 6)) * 8;
-      s16x8 v8 = QUANT ? dequant8(vraw[i], vsc) : vreg[i];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) vt_lds[(e0 + j) * VT_PITCH + kvr] = v8[j];
-    }
+    attn_write_tile<HD>(k_lds, vt_lds, tid, kreg, vreg);
   };
 
   load_tile(0);
@@ -180,112 +166,17 @@ __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
     __syncthreads();  // this tile's LDS image ready
 
     // wave fully above the shifted diagonal, or fully past the q tail.
-    // Tile 0 is never skipped for a live wave (0 <= pos + q0 + 31).
+    // Tile 0 is never skipped for a live wave (0 <= pos + q0 + 31), and kv 0
+    // is visible to every row (vis >= 0): attn_tile_step's m_run is finite
+    // from the first processed tile on.
     if (!wave_live || kv0 > pos + q0 + QB - 1) continue;
-
-    // ---- S^T = K Q^T : two 32-kv accumulators ----
-    f32x16 st[2];
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-      f32x16 acc = {};
-#pragma unroll
-      for (int kc = 0; kc < KC; ++kc) {
-        s16x8 kf = *reinterpret_cast<const s16x8*>(
-            (char*)k_lds + k_lds_off<HD>(32 * mb + ln, 16 * kc + 8 * hi));
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qfrag[kc], acc, 0, 0, 0);
-      }
-      st[mb] = acc;
-    }
-
-    // ---- online softmax over the 32 regs (all kv of this tile, own q) ----
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int kv = kv0 + 32 * mb + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        float sc = st[mb][r] * scale;
-        if (kv > vis) sc = -INFINITY;
-        st[mb][r] = sc;
-        tmax = fmaxf(tmax, sc);
-      }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    // kv 0 is visible to every row (vis >= 0) and sits in tile 0, which no
-    // live wave skips: m_new is finite from the first processed tile on, so
-    // exp(m_run - m_new) is exp(-inf) = 0 there and never exp(-inf + inf);
-    // a later tile that is fully masked for a row leaves m_new = m_run.
-    const float m_new = fmaxf(m_run, tmax);
-    const float alpha = __expf(m_run - m_new);
-    float psum = 0.f;
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float p = __expf(st[mb][r] - m_new);
-        st[mb][r] = p;
-        psum += p;
-      }
-    psum += __shfl_xor(psum, 32, 64);
-    l_run = l_run * alpha + psum;
-    m_run = m_new;
-#pragma unroll
-    for (int db = 0; db < DBLK; ++db)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ot[db][r] *= alpha;
-
-    // ---- pack P^T to bf16 B-fragments (pair-pack + half swap) ----
-    s16x8 pfrag[4];
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        unsigned c0 = pack_bf16x2(st[mb][8 * half + 0], st[mb][8 * half + 1]);
-        unsigned c1 = pack_bf16x2(st[mb][8 * half + 2], st[mb][8 * half + 3]);
-        unsigned c2 = pack_bf16x2(st[mb][8 * half + 4], st[mb][8 * half + 5]);
-        unsigned c3 = pack_bf16x2(st[mb][8 * half + 6], st[mb][8 * half + 7]);
-        auto r02 = __builtin_amdgcn_permlane32_swap(c0, c2, false, false);
-        auto r13 = __builtin_amdgcn_permlane32_swap(c1, c3, false, false);
-        unsigned frag[4] = {(unsigned)r02[0], (unsigned)r13[0], (unsigned)r02[1],
-                            (unsigned)r13[1]};
-        pfrag[2 * mb + half] = *reinterpret_cast<s16x8*>(frag);
-      }
-    }
-
-    // ---- O^T += V^T P^T ----
-#pragma unroll
-    for (int db = 0; db < DBLK; ++db) {
-#pragma unroll
-      for (int kc = 0; kc < 4; ++kc) {
-        s16x8 vf = *reinterpret_cast<const s16x8*>(
-            vt_lds + (32 * db + ln) * VT_PITCH + 16 * kc + 8 * hi);
-        ot[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pfrag[kc], ot[db], 0, 0, 0);
-      }
-    }
+    attn_tile_step<HD>(k_lds, vt_lds, qfrag, ot, m_run, l_run, kv0, scale, vis);
   }
 
   if (!wave_live) return;  // no barrier below this point
 
-  // ---- epilogue: normalize, transpose through LDS, coalesced store of the
-  // rows < s only ----
-  const float inv_l = l_run > 0.f ? 1.f / l_run : 0.f;
-  constexpr int OPITCH = HD + 8;
-#pragma unroll
-  for (int db = 0; db < DBLK; ++db)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int d = 32 * db + (r & 3) + 8 * (r >> 2) + 4 * hi;
-      ot_lds[wid][ln * OPITCH + d] = f2bf(ot[db][r] * inv_l);
-    }
-  __builtin_amdgcn_s_waitcnt(0);  // lgkmcnt(0): own-wave LDS writes visible
-#pragma unroll
-  for (int it = 0; it < QB * HD / 8 / 64; ++it) {
-    int c = it * 64 + lane;
-    int row = c / (HD / 8), e0 = (c % (HD / 8)) * 8;
-    if (q0 + row < s) {
-      s16x8 o8 = *reinterpret_cast<const s16x8*>(ot_lds[wid] + row * OPITCH + e0);
-      *reinterpret_cast<s16x8*>(og + qbase + (long long)(q0 + row) * q_ss + e0) = o8;
-    }
-  }
+  // only the rows < s are stored
+  attn_store_o<HD>(ot, l_run, ot_lds[wid], og + qbase, q_ss, q0, s);
 }
 
 torch::Tensor attn_prefill_impl(torch::Tensor q, torch::Tensor kcache,

@@ -267,6 +267,25 @@ def test_attention_noncausal():
     torch.testing.assert_close(o.float(), want, rtol=2e-2, atol=2e-2)
 
 
+@pytest.mark.parametrize("causal", [True, False])
+def test_attention_lse(causal):
+    """The stored log-sum-exp, directly (the backward only consumes it). S=256
+    is two workgroups and four kv tiles: skipped tiles and the rescale run."""
+    B, hq, hkv, S, hd = 1, 4, 2, 256, 64
+    q = rand_bf16(B, hq, S, hd, seed=23)
+    k = rand_bf16(B, hkv, S, hd, seed=24)
+    v = rand_bf16(B, hkv, S, hd, seed=25)
+    lse = _C.attn_fwd_ex(q, k, v, causal, "bhsd")[1]
+    kf = k.float().repeat_interleave(hq // hkv, dim=1)
+    scores = q.float() @ kf.transpose(-1, -2) / math.sqrt(hd)
+    if causal:
+        mask = torch.ones(S, S, dtype=torch.bool, device=DEV).tril()
+        scores = scores.masked_fill(~mask, float("-inf"))
+    want = torch.logsumexp(scores, dim=-1)
+    assert lse.shape == want.shape and lse.dtype == torch.float32
+    torch.testing.assert_close(lse, want, rtol=2e-2, atol=2e-2)
+
+
 # ---------------------------------------------------------------------------
 # End-to-end: tiny model steps on GPU with native ops
 # ---------------------------------------------------------------------------

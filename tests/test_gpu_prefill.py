@@ -84,6 +84,23 @@ def test_prefill_chunks_match_one_shot_flash_kernel():
     assert pos == S
 
 
+@pytest.mark.parametrize("shape", [(2, 8, 2, 128), (1, 4, 4, 64)],
+                         ids=lambda s: "-".join(map(str, s)))
+def test_prefill_aligned_equals_flash_kernel(shape):
+    """pos = 0, s = T_alloc = 256: no tail, no offset. Both kernels then run
+    the one shared tile step (attn_tile.h) over the same tiles."""
+    B, Hq, Hkv, D = shape
+    S = 256
+    q = rand_bf16(B, S, Hq, D, seed=10)
+    k = rand_bf16(B, S, Hkv, D, seed=11)
+    v = rand_bf16(B, S, Hkv, D, seed=12)
+    o = ops.attn_prefill(q, k, v, 0)
+    ref = ops.flash_attention(q, k, v, causal=True, layout="bshd")
+    print(f"{shape}: bit-equal to the flash kernel: {torch.equal(o, ref)}, "
+          f"max abs diff {(o.float() - ref.float()).abs().max().item():.3e}")
+    torch.testing.assert_close(o.float(), ref.float(), **TOL)
+
+
 def _bf16_model(name):
     model = models.build(name).to(DEV).bfloat16().eval()
     for buf in model.buffers():  # rope tables stay fp32
