@@ -85,6 +85,33 @@ class KVCache:
             self.k.index_copy_(1, pos, k)
             self.v.index_copy_(1, pos, v)
 
+    def append_rows(self, k: torch.Tensor, v: torch.Tensor, pos: torch.Tensor) -> None:
+        """Per-sequence single-row append (ragged batches): k/v [B, 1, Hkv, D]
+        go to cache row pos[b] of sequence b; pos is int64 [B] on the cache's
+        device. A pos[b] outside [0, T_max) writes nothing for that sequence
+        (the parking position of a finished one). Graph-capturable on the
+        native path; like append_at, does NOT advance the python-side counter."""
+        if k.shape[1] != 1 or pos.shape != (self.k.shape[0],):
+            raise ValueError("append_rows: k/v must be [B, 1, Hkv, D] and pos [B]")
+        if k.is_cuda and k.shape[-1] in (64, 128):
+            from hypha_amd import _C
+
+            _C.kv_append_rows_(k.contiguous(), v.contiguous(), self.k, self.v,
+                               self.k_scale, self.v_scale, pos)
+            return
+        # PyTorch fallback (CPU, other head dims): rows of the live sequences
+        live = ((pos >= 0) & (pos < self.k.shape[1])).nonzero().flatten()
+        rows = pos[live]
+        if self.quant == "fp8":
+            for x, dst, dst_scale in ((k, self.k, self.k_scale),
+                                      (v, self.v, self.v_scale)):
+                xq, scale = self._quantize_rows(x[live, 0])
+                dst.view(torch.uint8)[live, rows] = xq.view(torch.uint8)
+                dst_scale[live, rows] = scale
+        else:
+            self.k[live, rows] = k[live, 0]
+            self.v[live, rows] = v[live, 0]
+
     def _quantize_rows(self, x: torch.Tensor):
         amax = x.float().abs().amax(-1).clamp(min=1e-8)
         scale = amax / E4M3_MAX

@@ -87,7 +87,8 @@ class Attention(nn.Module):
         self.wv = nn.Linear(cfg.hidden_size, cfg.n_kv_heads * hd, bias=False)
         self.wo = nn.Linear(cfg.n_heads * hd, cfg.hidden_size, bias=False)
 
-    def forward(self, x, cos, sin, cache=None, pos: int = 0):
+    def forward(self, x, cos, sin, cache=None, pos: int = 0, seq_lens=None,
+                ragged=None):
         b, s, _ = x.shape
         cfg = self.cfg
         hd = cfg.head_dim
@@ -105,8 +106,19 @@ class Attention(nn.Module):
         # Decode (s==1) runs the native flash-decoding kernel; an aligned
         # first pass runs the MFMA flash kernel; ragged prompts and chunked
         # continuation run the cache-reading prefill kernel (ops.attn_prefill).
+        if ragged is not None:
+            # ragged decode step (s == 1): every sequence at its own position
+            o = ragged.attend(q, k, v, cos, sin, cache)
+            return self.wo(o.reshape(b, 1, -1))
         q, k = ops.apply_rope_qk(q, k, cos[pos:], sin[pos:], layout="bshd")
         t = cache.append(k, v)
+        if seq_lens is not None:
+            # right-padded batch: the pads' K/V rows are written like any
+            # other (decode overwrites them); the kernel skips what a short
+            # sequence does not have
+            o = ops.attn_prefill(q, cache.k, cache.v, pos, cache.k_scale,
+                                 cache.v_scale, seq_lens=seq_lens)
+            return self.wo(o.reshape(b, s, -1))
         if s == 1:
             o = ops.attn_decode(q[:, 0].contiguous(), cache.k, cache.v, t,
                                 cache.k_scale, cache.v_scale)
@@ -139,8 +151,10 @@ class Block(nn.Module):
         self.mlp_norm = RMSNorm(cfg.hidden_size, cfg.norm_eps)
         self.mlp = MLP(cfg)
 
-    def forward(self, x, cos, sin, cache=None, pos: int = 0):
-        attn_out = self.attn(self.attn_norm(x), cos, sin, cache=cache, pos=pos)
+    def forward(self, x, cos, sin, cache=None, pos: int = 0, seq_lens=None,
+                ragged=None):
+        attn_out = self.attn(self.attn_norm(x), cos, sin, cache=cache, pos=pos,
+                             seq_lens=seq_lens, ragged=ragged)
         # fused residual-add + norm: one kernel writes the residual stream
         # and the normalized MLP input (saves an elementwise pass per block)
         x, n2 = ops.add_rmsnorm(x, attn_out, self.mlp_norm.weight,
@@ -211,19 +225,157 @@ class LlamaForCausalLM(nn.Module):
         return loss
 
 
+class RaggedStep:
+    """Per-sequence state of one ragged decode step, shared by every layer.
+
+    n_cache int64 [B]: rows sequence b has in the cache = the position of its
+    current token; alive bool [B]. A live sequence rotates at n_cache[b],
+    appends at row n_cache[b] and attends over n_cache[b] + 1 rows. A finished
+    one parks its append out of range (nothing written) and attends over 0
+    rows (exact zeros, no cache read). All device tensors: building one costs
+    no host round trip, so a step can be graph-captured."""
+
+    __slots__ = ("rope_pos", "append_pos", "attn_lens", "max_len")
+
+    def __init__(self, n_cache: torch.Tensor, alive: torch.Tensor, t_alloc: int,
+                 rope_rows: int, max_len: int | None = None):
+        self.rope_pos = n_cache.clamp(max=rope_rows - 1)
+        self.append_pos = torch.where(alive, n_cache, torch.full_like(n_cache, t_alloc))
+        self.attn_lens = torch.where(alive, n_cache + 1,
+                                     torch.zeros_like(n_cache)).to(torch.int32)
+        self.max_len = max_len
+
+    def attend(self, q, k, v, cos, sin, cache):
+        q, k = ops.apply_rope_qk_at(q, k, cos, sin, self.rope_pos)
+        cache.append_rows(k, v, self.append_pos)
+        return ops.attn_decode_varlen(q[:, 0].contiguous(), cache.k, cache.v,
+                                      self.attn_lens, cache.k_scale, cache.v_scale,
+                                      max_len=self.max_len)
+
+
+def check_prompt_lens(prompt_lens, batch: int, s: int, device) -> torch.Tensor:
+    """prompt_lens (list or tensor, int [B], 1 <= L_b <= s) -> int64 [B] on device."""
+    lens = torch.as_tensor(prompt_lens).reshape(-1).to(torch.long).cpu()
+    if lens.numel() != batch:
+        raise ValueError(f"prompt_lens has {lens.numel()} entries for a batch of {batch}")
+    if int(lens.min()) < 1 or int(lens.max()) > s:
+        raise ValueError(f"prompt_lens must lie in [1, {s}], got {lens.tolist()}")
+    return lens.to(device)
+
+
+def prefill_ragged(model, caches, input_ids, lens, prefill_chunk):
+    """Prefill a right-padded batch (possibly in chunks) and return the hidden
+    row of every sequence's LAST prompt token [B, 1, h], taken from whichever
+    chunk holds it. lens int64 [B] on the device."""
+    b, s = input_ids.shape
+    seq_lens = lens.to(torch.int32)
+    step = s if prefill_chunk is None else prefill_chunk
+    rows = torch.arange(b, device=input_ids.device)
+    last = None
+    for p0 in range(0, s, step):
+        x = model.embed(input_ids[:, p0:p0 + step])
+        for blk, cache in zip(model.blocks, caches):
+            x = blk(x, model.rope_cos, model.rope_sin, cache=cache, pos=p0,
+                    seq_lens=seq_lens)
+        idx = lens - 1 - p0
+        here = (idx >= 0) & (idx < x.shape[1])
+        picked = x[rows, idx.clamp(0, x.shape[1] - 1)]
+        last = picked if last is None else torch.where(here[:, None], picked, last)
+    return last[:, None]
+
+
+def _sample(logits, temperature, top_k, gen):
+    if temperature <= 0:
+        return logits.argmax(-1, keepdim=True)
+    logits = logits / temperature
+    if top_k > 0:
+        kth = logits.topk(top_k, dim=-1).values[..., -1, None]
+        logits = logits.masked_fill(logits < kth, float("-inf"))
+    probs = torch.softmax(logits.float(), dim=-1)
+    return torch.multinomial(probs, 1, generator=gen)
+
+
+def _generate_ragged(self, input_ids, max_new_tokens, temperature, top_k, seed,
+                     kv_quant, prefill_chunk, prompt_lens, eos_token_id,
+                     pad_token_id):
+    """Generation over a right-padded batch and/or with a stop token.
+    Returns (tokens [B, s + max_new_tokens], lens [B])."""
+    from .kv_cache import KVCache
+
+    self.eval()
+    b, s = input_ids.shape
+    dev = input_ids.device
+    total = s + max_new_tokens
+    n_cache = check_prompt_lens([s] * b if prompt_lens is None else prompt_lens,
+                                b, s, dev)
+    # tokens: each prompt, pads everywhere else
+    tokens = torch.full((b, total), pad_token_id, dtype=input_ids.dtype, device=dev)
+    in_prompt = torch.arange(s, device=dev)[None, :] < n_cache[:, None]
+    tokens[:, :s] = torch.where(in_prompt, input_ids, tokens[:, :s])
+    lens_out = n_cache.clone()
+    if max_new_tokens <= 0:
+        return tokens, lens_out
+    caches = [KVCache(b, total, self.cfg.n_kv_heads, self.cfg.head_dim, dev,
+                      dtype=self.embed.weight.dtype, quant=kv_quant)
+              for _ in self.blocks]
+    gen = None
+    if seed is not None:
+        gen = torch.Generator(device=dev).manual_seed(seed)
+    alive = torch.ones(b, dtype=torch.bool, device=dev)
+    x = prefill_ragged(self, caches, input_ids, n_cache, prefill_chunk)
+    for i in range(max_new_tokens):
+        x = self.norm(x)
+        if self.lm_head is not None:
+            logits = self.lm_head(x)[:, 0]
+        else:
+            logits = torch.nn.functional.linear(x, self.embed.weight)[:, 0]
+        nxt = _sample(logits, temperature, top_k, gen)  # [B, 1]
+        # a live sequence's new token goes directly after what it has
+        at = n_cache.clamp(max=total - 1)[:, None]
+        tokens.scatter_(1, at, torch.where(alive[:, None], nxt, tokens.gather(1, at)))
+        lens_out = torch.where(alive, n_cache + 1, lens_out)
+        if eos_token_id is not None:
+            alive = alive & (nxt[:, 0] != eos_token_id)
+            if not bool(alive.any()):
+                break
+        if i == max_new_tokens - 1:
+            break
+        step = RaggedStep(n_cache, alive, total, self.rope_cos.shape[0],
+                          max_len=min(s + i + 1, total))
+        x = self.embed(torch.where(alive[:, None], nxt, torch.full_like(nxt, pad_token_id)))
+        for blk, cache in zip(self.blocks, caches):
+            x = blk(x, self.rope_cos, self.rope_sin, cache=cache, ragged=step)
+        n_cache = n_cache + alive.to(n_cache.dtype)
+    return tokens, lens_out
+
+
 @torch.no_grad()
 def _generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
               temperature: float = 0.0, top_k: int = 0,
               seed: int | None = None, kv_quant: str | None = None,
-              prefill_chunk: int | None = None) -> torch.Tensor:
+              prefill_chunk: int | None = None, prompt_lens=None,
+              eos_token_id: int | None = None, pad_token_id: int = 0):
     """Autoregressive generation with a per-layer KV cache (inference parity:
     the reference serves inference through the same executor surface).
     prefill_chunk feeds the prompt in pieces of at most that many tokens
-    (activation memory bounded by the chunk); None prefills in one pass."""
+    (activation memory bounded by the chunk); None prefills in one pass.
+
+    prompt_lens (list or tensor, int [B], 1 <= L_b <= s) makes input_ids a
+    RIGHT-PADDED batch: row b holds L_b prompt tokens, then anything. The call
+    then returns (tokens [B, s + max_new_tokens], lens [B]): each sequence's
+    new tokens directly after its own prompt, pad_token_id everywhere else,
+    lens[b] its final valid length. eos_token_id stops a sequence once it
+    emits that token (kept; pads after it); without prompt_lens the call then
+    still returns only tokens."""
     from .kv_cache import KVCache
 
     if prefill_chunk is not None and prefill_chunk < 1:
         raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
+    if prompt_lens is not None or eos_token_id is not None:
+        tokens, lens = _generate_ragged(
+            self, input_ids, max_new_tokens, temperature, top_k, seed, kv_quant,
+            prefill_chunk, prompt_lens, eos_token_id, pad_token_id)
+        return (tokens, lens) if prompt_lens is not None else tokens
     self.eval()
     b, s = input_ids.shape
     max_len = s + max_new_tokens
@@ -258,15 +410,7 @@ def _generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
             logits = self.lm_head(x)[:, 0]
         else:
             logits = torch.nn.functional.linear(x, self.embed.weight)[:, 0]
-        if temperature <= 0:
-            nxt = logits.argmax(-1, keepdim=True)
-        else:
-            logits = logits / temperature
-            if top_k > 0:
-                kth = logits.topk(top_k, dim=-1).values[..., -1, None]
-                logits = logits.masked_fill(logits < kth, float("-inf"))
-            probs = torch.softmax(logits.float(), dim=-1)
-            nxt = torch.multinomial(probs, 1, generator=gen)
+        nxt = _sample(logits, temperature, top_k, gen)
         pos += x_in.shape[1]
         tokens = torch.cat([tokens, nxt], dim=1)
         x_in = nxt

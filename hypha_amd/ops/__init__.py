@@ -54,7 +54,9 @@ def use_native(*tensors: torch.Tensor) -> bool:
 from .interface import (  # noqa: E402
     add_rmsnorm,
     apply_rope_qk,
+    apply_rope_qk_at,
     attn_decode,
+    attn_decode_varlen,
     attn_prefill,
     cross_entropy_loss,
     extract_delta,
@@ -78,7 +80,9 @@ __all__ = [
     "gelu",
     "add_rmsnorm",
     "apply_rope_qk",
+    "apply_rope_qk_at",
     "attn_decode",
+    "attn_decode_varlen",
     "attn_prefill",
     "swiglu",
     "flash_attention",

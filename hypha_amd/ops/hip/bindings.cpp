@@ -104,6 +104,22 @@ torch::Tensor attn_decode_fp8_graph(torch::Tensor q, torch::Tensor kcache,
 void kv_append_fp8_(torch::Tensor k, torch::Tensor v, torch::Tensor k8,
                     torch::Tensor v8, torch::Tensor kscale, torch::Tensor vscale,
                     torch::Tensor pos);
+// per-sequence lengths / positions (right-padded batches)
+torch::Tensor attn_decode_varlen(torch::Tensor q, torch::Tensor kcache,
+                                 torch::Tensor vcache, torch::Tensor lens, long max_len);
+torch::Tensor attn_decode_varlen_fp8(torch::Tensor q, torch::Tensor kcache,
+                                     torch::Tensor vcache, torch::Tensor kscale,
+                                     torch::Tensor vscale, torch::Tensor lens,
+                                     long max_len);
+void kv_append_rows_(torch::Tensor k, torch::Tensor v, torch::Tensor kcache,
+                     torch::Tensor vcache, std::optional<torch::Tensor> kscale,
+                     std::optional<torch::Tensor> vscale, torch::Tensor pos);
+torch::Tensor attn_prefill_varlen(torch::Tensor q, torch::Tensor kcache,
+                                  torch::Tensor vcache, long pos, torch::Tensor seq_lens);
+torch::Tensor attn_prefill_varlen_fp8(torch::Tensor q, torch::Tensor kcache,
+                                      torch::Tensor vcache, torch::Tensor kscale,
+                                      torch::Tensor vscale, long pos,
+                                      torch::Tensor seq_lens);
 // prefill.hip (ragged / chunked prefill attention over the KV cache)
 torch::Tensor attn_prefill(torch::Tensor q, torch::Tensor kcache, torch::Tensor vcache,
                            long pos);
@@ -160,5 +176,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kv_append_fp8_", &kv_append_fp8_);
   m.def("attn_prefill", &attn_prefill);
   m.def("attn_prefill_fp8", &attn_prefill_fp8);
+  m.def("attn_decode_varlen", &attn_decode_varlen);
+  m.def("attn_decode_varlen_fp8", &attn_decode_varlen_fp8);
+  m.def("kv_append_rows_", &kv_append_rows_);
+  m.def("attn_prefill_varlen", &attn_prefill_varlen);
+  m.def("attn_prefill_varlen_fp8", &attn_prefill_varlen_fp8);
   m.def("skinny_gemm", &skinny_gemm);
 }

@@ -42,10 +42,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
     const short* __restrict__ vg, const float* __restrict__ kscale,
     const float* __restrict__ vscale, float* __restrict__ partial_o,
     float* __restrict__ partial_ml, int B, int Hq, int Hkv, int T_alloc, int t_in,
-    const int* __restrict__ t_dev, int nsplits, float scale) {
-  // hipGraph mode: the valid length lives in device memory so one captured
-  // graph serves every decode step (t grows between replays)
-  const int t = t_dev ? *t_dev : t_in;
+    const int* __restrict__ t_dev, int t_stride, int nsplits, float scale) {
   constexpr int PITCH = HD + 8;  // shorts; 16B-aligned, conflict-free b128
   __shared__ __attribute__((aligned(16))) short k_t[TILE * PITCH];
   __shared__ __attribute__((aligned(16))) short v_t[TILE * PITCH];
@@ -61,7 +58,15 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
   const int G = Hq / Hkv;
   constexpr int GWMAX = 2;  // compile-time bound: supports G <= 8
 
-  // this split's kv range (tile-aligned chunks)
+  // hipGraph mode: the valid length lives in device memory so one captured
+  // graph serves every decode step (t grows between replays). t_stride 0:
+  // one length for the batch; t_stride 1: one per sequence (varlen), so the
+  // split range below is this workgroup's own sequence's. Clamped: a length
+  // from device memory must never index past the cache.
+  const int t = t_dev ? min(max(t_dev[b * t_stride], 0), T_alloc) : t_in;
+
+  // this split's kv range (tile-aligned chunks); a sequence shorter than
+  // the batch's longest leaves its later splits empty (s0 >= s1)
   const int chunk = ((t + nsplits - 1) / nsplits + TILE - 1) / TILE * TILE;
   const int s0 = split * chunk;
   const int s1 = min(t, s0 + chunk);
@@ -200,6 +205,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
 }
 
 // ---- split-merge: one block per (b, hq); thread per head-dim element ----
+// An empty split wrote (m=-1e30, l=0, o=0): next to a non-empty one its
+// factor exp(-1e30 - m_star) is 0. A sequence of length 0 (varlen: a finished
+// sequence) has ONLY empty splits: m_star = -1e30, every f = exp(0) = 1,
+// num = 0, den = 0, and 0 / max(den, 1e-30) is an exact +0 in every lane.
 template <int HD>
 __global__ __launch_bounds__(128) void attn_decode_reduce_kernel(
     const float* __restrict__ partial_o, const float* __restrict__ partial_ml,
@@ -228,7 +237,8 @@ torch::Tensor attn_decode_impl(torch::Tensor q, torch::Tensor kcache,
                                torch::Tensor vcache, long t,
                                const torch::Tensor* t_dev,
                                const torch::Tensor* kscale = nullptr,
-                               const torch::Tensor* vscale = nullptr) {
+                               const torch::Tensor* vscale = nullptr,
+                               int t_stride = 0, long max_len = -1) {
   TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16 && q.dim() == 3);
   TORCH_CHECK(kcache.dim() == 4 && kcache.is_contiguous() && vcache.is_contiguous());
   const bool quant = kcache.dtype() == torch::kFloat8_e4m3fn;
@@ -240,12 +250,19 @@ torch::Tensor attn_decode_impl(torch::Tensor q, torch::Tensor kcache,
   TORCH_CHECK(Hq % Hkv == 0 && (HD == 64 || HD == 128), "decode: unsupported shape");
   TORCH_CHECK(Hq / Hkv <= 8, "decode: GQA group > 8 not supported");
   TORCH_CHECK(q.is_contiguous());
+  TORCH_CHECK(!t_dev || (t_dev->dtype() == torch::kInt32 && t_dev->is_cuda() &&
+                         t_dev->is_contiguous() &&
+                         t_dev->numel() >= (t_stride ? B : 1)),
+              "decode: device lengths must be int32, one per sequence");
+  TORCH_CHECK(max_len < 0 || (max_len >= 1 && max_len <= T_alloc),
+              "decode: bad max_len");
   const int* t_ptr = t_dev ? t_dev->data_ptr<int>() : nullptr;
 
   // enough splits to fill the chip, but >= 2 tiles of work per split; in
-  // graph mode (t_dev) size for the worst case T_alloc so one capture
-  // covers every step
-  long t_sz = t_dev ? T_alloc : t;
+  // graph mode (t_dev) size for the worst case T_alloc (or the caller's
+  // bound max_len) so one capture covers every step. The kernel derives its
+  // chunk from the length it reads, so nsplits only sizes the grid.
+  long t_sz = t_dev ? (max_len > 0 ? max_len : T_alloc) : t;
   int nsplits = (int)std::min<long>((512 + B * Hkv - 1) / (B * Hkv),
                                     std::max<long>(1, (t_sz + 2 * TILE - 1) / (2 * TILE)));
   auto fopts = q.options().dtype(torch::kFloat32);
@@ -266,7 +283,7 @@ torch::Tensor attn_decode_impl(torch::Tensor q, torch::Tensor kcache,
                        (const short*)vcache.data_ptr(), ksp, vsp,                      \
                        partial_o.data_ptr<float>(),                                    \
                        partial_ml.data_ptr<float>(), B, Hq, Hkv, T_alloc, (int)t,      \
-                       t_ptr, nsplits, scale);                                         \
+                       t_ptr, t_stride, nsplits, scale);                               \
     hipLaunchKernelGGL(attn_decode_reduce_kernel<HDV>, dim3(B* Hq), dim3(128), 0,      \
                        stream, partial_o.data_ptr<float>(),                            \
                        partial_ml.data_ptr<float>(), (short*)out.data_ptr(), B, Hq,    \
@@ -313,6 +330,27 @@ torch::Tensor attn_decode_fp8_graph(torch::Tensor q, torch::Tensor kcache,
                           &vscale);
 }
 
+// Per-sequence lengths: lens int32 [B] on the device, lens[b] = valid rows
+// of sequence b INCLUDING the current token, read at kernel time (graph-
+// capturable as is). lens[b] == 0 returns exact zeros for that sequence and
+// reads none of its cache. max_len (host, <= 0: T_alloc) only sizes nsplits.
+torch::Tensor attn_decode_varlen(torch::Tensor q, torch::Tensor kcache,
+                                 torch::Tensor vcache, torch::Tensor lens,
+                                 long max_len) {
+  TORCH_CHECK(lens.dim() == 1 && lens.size(0) == q.size(0), "decode: lens must be [B]");
+  return attn_decode_impl(q, kcache, vcache, kcache.size(1), &lens, nullptr, nullptr,
+                          1, max_len > 0 ? max_len : -1);
+}
+
+torch::Tensor attn_decode_varlen_fp8(torch::Tensor q, torch::Tensor kcache,
+                                     torch::Tensor vcache, torch::Tensor kscale,
+                                     torch::Tensor vscale, torch::Tensor lens,
+                                     long max_len) {
+  TORCH_CHECK(lens.dim() == 1 && lens.size(0) == q.size(0), "decode: lens must be [B]");
+  return attn_decode_impl(q, kcache, vcache, kcache.size(1), &lens, &kscale, &vscale,
+                          1, max_len > 0 ? max_len : -1);
+}
+
 namespace {
 
 // Fused single-token fp8 KV append: one launch quantizes the new k AND v
@@ -324,7 +362,7 @@ __global__ __launch_bounds__(64) void kv_append_fp8_kernel(
     const short* __restrict__ kin, const short* __restrict__ vin,
     unsigned char* __restrict__ k8, unsigned char* __restrict__ v8,
     float* __restrict__ kscale, float* __restrict__ vscale,
-    const long long* __restrict__ pos, int B, int Hkv, int T_alloc) {
+    const long long* __restrict__ pos, int pos_stride, int B, int Hkv, int T_alloc) {
   const int bh = blockIdx.x;       // (b * Hkv + h)
   const int which = blockIdx.y;    // 0 = k, 1 = v
   const int l = threadIdx.x;
@@ -332,7 +370,11 @@ __global__ __launch_bounds__(64) void kv_append_fp8_kernel(
   unsigned char* dst8 = which ? v8 : k8;
   float* dsts = which ? vscale : kscale;
   const int b = bh / Hkv, h = bh % Hkv;
-  const long long p = *pos;
+  // pos_stride 0: one position for the batch; 1: one per sequence. A
+  // position outside the cache writes nothing (uniform over the block): the
+  // parking position of a finished sequence.
+  const long long p = pos[b * pos_stride];
+  if (p < 0 || p >= T_alloc) return;
   const long long row = ((long long)b * T_alloc + p) * Hkv + h;
 
   float vals[HD / 64];
@@ -344,15 +386,68 @@ __global__ __launch_bounds__(64) void kv_append_fp8_kernel(
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-  const float scale = fmaxf(mx, 1e-8f) / 448.0f;
-  const float inv = 1.0f / scale;
+  // The bytes and the scale KVCache._quantize_rows writes for this row on the
+  // GPU, bit for bit, so that a row appended here and one appended through
+  // the PyTorch path are the same row: there the scale is amax times the
+  // fp32 reciprocal of 448 (how a tensor is divided by a host scalar), and
+  // each element is DIVIDED by the scale. (x * (1 / scale) rounds twice and
+  // lands on another e4m3 byte in about 2% of bf16 rows.)
+  const float scale = fmaxf(mx, 1e-8f) * (1.0f / 448.0f);
   if (l == 0) dsts[row] = scale;
 #pragma unroll
   for (int i = 0; i < HD / 64; ++i) {
-    float a = fminf(fmaxf(vals[i] * inv, -448.f), 448.f);
+    float a = fminf(fmaxf(vals[i] / scale, -448.f), 448.f);
     dst8[row * HD + l + 64 * i] =
         (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(a, a, 0, false) & 0xff);
   }
+}
+
+// bf16 cache: the row of sequence b (Hkv * HD contiguous elements in bshd)
+// is copied as 16-byte vectors to cache row pos[b]; blockIdx.y: 0 = k, 1 = v.
+__global__ __launch_bounds__(256) void kv_append_rows_bf16_kernel(
+    const short* __restrict__ kin, const short* __restrict__ vin,
+    short* __restrict__ kc, short* __restrict__ vc,
+    const long long* __restrict__ pos, int row_elems, int T_alloc) {
+  const int b = blockIdx.x;
+  const long long p = pos[b];
+  if (p < 0 || p >= T_alloc) return;  // parked sequence: nothing written
+  const short* src = (blockIdx.y ? vin : kin) + (long long)b * row_elems;
+  short* dst = (blockIdx.y ? vc : kc) + ((long long)b * T_alloc + p) * row_elems;
+  for (int c = threadIdx.x * 8; c < row_elems; c += 256 * 8)
+    *reinterpret_cast<s16x8*>(dst + c) = *reinterpret_cast<const s16x8*>(src + c);
+}
+
+void kv_append_fp8_launch(torch::Tensor k, torch::Tensor v, torch::Tensor k8,
+                          torch::Tensor v8, torch::Tensor kscale, torch::Tensor vscale,
+                          torch::Tensor pos, int pos_stride) {
+  const int B = k8.size(0), T_alloc = k8.size(1), Hkv = k8.size(2), HD = k8.size(3);
+  TORCH_CHECK(k.is_cuda() && v.is_cuda() && k.dtype() == torch::kBFloat16 &&
+              v.dtype() == torch::kBFloat16);
+  TORCH_CHECK(k.numel() == (long long)B * Hkv * HD && k.is_contiguous());
+  TORCH_CHECK(v.numel() == k.numel() && v.is_contiguous());
+  TORCH_CHECK(pos.dtype() == torch::kInt64 && pos.is_cuda() && pos.is_contiguous() &&
+              pos.numel() >= (pos_stride ? B : 1));
+  TORCH_CHECK(HD == 64 || HD == 128);
+  TORCH_CHECK(k8.dtype() == torch::kFloat8_e4m3fn && k8.is_contiguous() &&
+              v8.is_contiguous() && v8.sizes() == k8.sizes() && v8.dtype() == k8.dtype());
+  for (const torch::Tensor* sc : {&kscale, &vscale})
+    TORCH_CHECK(sc->is_cuda() && sc->dtype() == torch::kFloat32 && sc->is_contiguous() &&
+                sc->numel() == (long long)B * T_alloc * Hkv);
+  hipStream_t stream = hypha_stream();
+  if (HD == 128)
+    hipLaunchKernelGGL(kv_append_fp8_kernel<128>, dim3(B * Hkv, 2), dim3(64), 0,
+                       stream, (const short*)k.data_ptr(), (const short*)v.data_ptr(),
+                       (unsigned char*)k8.data_ptr(), (unsigned char*)v8.data_ptr(),
+                       kscale.data_ptr<float>(), vscale.data_ptr<float>(),
+                       (const long long*)pos.data_ptr<int64_t>(), pos_stride, B, Hkv,
+                       T_alloc);
+  else
+    hipLaunchKernelGGL(kv_append_fp8_kernel<64>, dim3(B * Hkv, 2), dim3(64), 0,
+                       stream, (const short*)k.data_ptr(), (const short*)v.data_ptr(),
+                       (unsigned char*)k8.data_ptr(), (unsigned char*)v8.data_ptr(),
+                       kscale.data_ptr<float>(), vscale.data_ptr<float>(),
+                       (const long long*)pos.data_ptr<int64_t>(), pos_stride, B, Hkv,
+                       T_alloc);
 }
 
 }  // namespace
@@ -362,21 +457,40 @@ __global__ __launch_bounds__(64) void kv_append_fp8_kernel(
 void kv_append_fp8_(torch::Tensor k, torch::Tensor v, torch::Tensor k8,
                     torch::Tensor v8, torch::Tensor kscale, torch::Tensor vscale,
                     torch::Tensor pos) {
-  const int B = k8.size(0), T_alloc = k8.size(1), Hkv = k8.size(2), HD = k8.size(3);
-  TORCH_CHECK(k.numel() == (long long)B * Hkv * HD && k.is_contiguous());
-  TORCH_CHECK(pos.dtype() == torch::kInt64 && pos.is_cuda());
-  TORCH_CHECK(HD == 64 || HD == 128);
-  hipStream_t stream = hypha_stream();
-  if (HD == 128)
-    hipLaunchKernelGGL(kv_append_fp8_kernel<128>, dim3(B * Hkv, 2), dim3(64), 0,
-                       stream, (const short*)k.data_ptr(), (const short*)v.data_ptr(),
-                       (unsigned char*)k8.data_ptr(), (unsigned char*)v8.data_ptr(),
-                       kscale.data_ptr<float>(), vscale.data_ptr<float>(),
-                       (const long long*)pos.data_ptr<int64_t>(), B, Hkv, T_alloc);
-  else
-    hipLaunchKernelGGL(kv_append_fp8_kernel<64>, dim3(B * Hkv, 2), dim3(64), 0,
-                       stream, (const short*)k.data_ptr(), (const short*)v.data_ptr(),
-                       (unsigned char*)k8.data_ptr(), (unsigned char*)v8.data_ptr(),
-                       kscale.data_ptr<float>(), vscale.data_ptr<float>(),
-                       (const long long*)pos.data_ptr<int64_t>(), B, Hkv, T_alloc);
+  kv_append_fp8_launch(k, v, k8, v8, kscale, vscale, pos, 0);
+}
+
+// Per-sequence single-row append: k/v [B, 1, Hkv, D] bf16 go to cache row
+// pos[b] of sequence b (pos int64 [B] on the device; graph-capturable). bf16
+// cache: vector copy; fp8 cache (kscale/vscale given): quantized exactly as
+// kv_append_fp8_ does. pos[b] outside [0, T_alloc) writes nothing for b.
+void kv_append_rows_(torch::Tensor k, torch::Tensor v, torch::Tensor kcache,
+                     torch::Tensor vcache, std::optional<torch::Tensor> kscale,
+                     std::optional<torch::Tensor> vscale, torch::Tensor pos) {
+  TORCH_CHECK(kcache.dim() == 4 && kcache.is_cuda(), "append_rows: cache [B, T_alloc, Hkv, D]");
+  const long B = kcache.size(0), T_alloc = kcache.size(1), Hkv = kcache.size(2),
+             HD = kcache.size(3);
+  TORCH_CHECK(pos.dim() == 1 && pos.size(0) == B, "append_rows: pos must be int64 [B]");
+  if (kcache.dtype() == torch::kFloat8_e4m3fn) {
+    TORCH_CHECK(kscale.has_value() && vscale.has_value(),
+                "append_rows: fp8 cache needs row scales");
+    kv_append_fp8_launch(k, v, kcache, vcache, *kscale, *vscale, pos, 1);
+    return;
+  }
+  TORCH_CHECK(kcache.dtype() == torch::kBFloat16 && kcache.is_contiguous() &&
+                  vcache.is_cuda() && vcache.is_contiguous() &&
+                  vcache.sizes() == kcache.sizes() && vcache.dtype() == kcache.dtype(),
+              "append_rows: caches must be contiguous bf16 of one shape");
+  TORCH_CHECK(k.is_cuda() && v.is_cuda() && k.dtype() == torch::kBFloat16 &&
+                  v.dtype() == torch::kBFloat16 && k.is_contiguous() && v.is_contiguous() &&
+                  k.numel() == B * Hkv * HD && v.numel() == k.numel(),
+              "append_rows: k/v must be contiguous bf16 [B, 1, Hkv, D]");
+  TORCH_CHECK(pos.dtype() == torch::kInt64 && pos.is_cuda() && pos.is_contiguous());
+  TORCH_CHECK(HD % 8 == 0 && Hkv * HD < (1L << 31) && B <= 65535 * 32768L,
+              "append_rows: unsupported shape");
+  hipLaunchKernelGGL(kv_append_rows_bf16_kernel, dim3((unsigned)B, 2), dim3(256), 0,
+                     hypha_stream(), (const short*)k.data_ptr(), (const short*)v.data_ptr(),
+                     (short*)kcache.data_ptr(), (short*)vcache.data_ptr(),
+                     (const long long*)pos.data_ptr<int64_t>(), (int)(Hkv * HD),
+                     (int)T_alloc);
 }

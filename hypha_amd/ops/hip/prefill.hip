@@ -19,6 +19,11 @@
 //    p = 0 times a NaN V would still poison O);
 //  * QUANT=true dequantizes e4m3 rows (per-row fp32 scale) while writing the
 //    LDS images, as decode.hip does, so the MFMA phases are shared.
+//  * seq_lens (optional, int32 [B], right-padded batches): sequence b is
+//    valid for len_b = clamp(seq_lens[b], 0, pos + s) rows, so this chunk
+//    holds s_b = max(0, len_b - pos) live q rows. s_b and len_b replace s and
+//    t in every bound below; a workgroup with no live row returns at once,
+//    and the (pre-zeroed) output rows >= s_b are never written.
 // No lse, no backward. Grid (ceil(s/128), B*Hq): a short chunk against a
 // long prefix runs few workgroups (no split-KV).
 
@@ -49,7 +54,7 @@ __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
     const short* __restrict__ qg, const void* __restrict__ kgv,
     const void* __restrict__ vgv, const float* __restrict__ kscale,
     const float* __restrict__ vscale, short* __restrict__ og, int Hq, int Hkv,
-    int s, int pos, int T_alloc, float scale) {
+    int s, int pos, int T_alloc, float scale, const int* __restrict__ seq_lens) {
   constexpr int KC = HD / 16;        // 16-wide k chunks over head dim
   constexpr int DBLK = HD / 32;      // 32-row d blocks
   __shared__ __attribute__((aligned(16))) short k_lds[KVB * HD];
@@ -66,27 +71,31 @@ __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
   const int b = bh / Hq;
   const int hq = bh % Hq;
   const int hkv = hq / (Hq / Hkv);
-  const int t = pos + s;  // valid cache rows
+  const int q0wg = blockIdx.x * WGQ;
+  // valid cache rows / live q rows of this chunk: the batch's (pos + s, s),
+  // or this sequence's own when lengths are given
+  const int len_b = seq_lens ? min(max(seq_lens[b], 0), pos + s) : pos + s;
+  const int s_b = max(0, len_b - pos);
+  if (q0wg >= s_b) return;  // uniform over the workgroup; before any barrier
   const long long q_ss = (long long)Hq * HD;
   const long long qbase = (long long)b * s * q_ss + (long long)hq * HD;
   const long long kvrow0 = (long long)b * T_alloc;  // cache row index of kv 0
 
-  const int q0wg = blockIdx.x * WGQ;
   const int q0 = q0wg + wid * QB;   // this wave's q rows
   const int qrow = q0 + ln;         // this lane's q row (its S^T column)
-  const bool wave_live = q0 < s;    // a wave past the ragged tail only stages
-  // last kv index this lane's row may see; rows >= s (never stored) are
+  const bool wave_live = q0 < s_b;  // a wave past the ragged tail only stages
+  // last kv index this lane's row may see; rows >= s_b (never stored) are
   // clamped to the valid prefix so their state stays finite too
-  const int vis = min(pos + qrow, t - 1);
-  // exclusive kv bound of this workgroup: >= 1, <= t <= T_alloc
-  const int kv_end = min(t, pos + q0wg + WGQ);
+  const int vis = min(pos + qrow, len_b - 1);
+  // exclusive kv bound of this workgroup: >= 1, <= len_b <= T_alloc
+  const int kv_end = min(len_b, pos + q0wg + WGQ);
 
   // ---- Q fragments: B operand of S^T = mfma(K, Q); lane ln = q column ----
   s16x8 qfrag[KC];
 #pragma unroll
   for (int kc = 0; kc < KC; ++kc) {
     s16x8 qv = {};
-    if (qrow < s)
+    if (qrow < s_b)
       qv = *reinterpret_cast<const s16x8*>(qg + qbase + (long long)qrow * q_ss +
                                            16 * kc + 8 * hi);
     qfrag[kc] = qv;
@@ -175,13 +184,14 @@ __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
 
   if (!wave_live) return;  // no barrier below this point
 
-  // only the rows < s are stored
-  attn_store_o<HD>(ot, l_run, ot_lds[wid], og + qbase, q_ss, q0, s);
+  // only the rows < s_b are stored
+  attn_store_o<HD>(ot, l_run, ot_lds[wid], og + qbase, q_ss, q0, s_b);
 }
 
 torch::Tensor attn_prefill_impl(torch::Tensor q, torch::Tensor kcache,
                                 torch::Tensor vcache, const torch::Tensor* kscale,
-                                const torch::Tensor* vscale, long pos) {
+                                const torch::Tensor* vscale, long pos,
+                                const torch::Tensor* seq_lens = nullptr) {
   TORCH_CHECK(q.is_cuda() && kcache.is_cuda() && vcache.is_cuda(),
               "prefill: tensors must be on the GPU");
   TORCH_CHECK(q.dim() == 4 && q.dtype() == torch::kBFloat16 && q.is_contiguous(),
@@ -214,7 +224,17 @@ torch::Tensor attn_prefill_impl(torch::Tensor q, torch::Tensor kcache,
     vsp = vscale->data_ptr<float>();
   }
 
-  auto o = torch::empty_like(q);
+  const int* lens_p = nullptr;
+  if (seq_lens) {
+    TORCH_CHECK(seq_lens->is_cuda() && seq_lens->dtype() == torch::kInt32 &&
+                    seq_lens->is_contiguous() && seq_lens->dim() == 1 &&
+                    seq_lens->size(0) == B,
+                "prefill: seq_lens must be contiguous int32 [B] on the GPU");
+    lens_p = seq_lens->data_ptr<int>();
+  }
+
+  // with lengths, the rows past a sequence's end are never written: exact zeros
+  auto o = seq_lens ? torch::zeros_like(q) : torch::empty_like(q);
   const float scale = 1.0f / sqrtf((float)HD);
   dim3 grid((unsigned)((s + WGQ - 1) / WGQ), (unsigned)(B * Hq));
   hipStream_t stream = hypha_stream();
@@ -223,7 +243,8 @@ torch::Tensor attn_prefill_impl(torch::Tensor q, torch::Tensor kcache,
   hipLaunchKernelGGL((attn_prefill_kernel<HDV, QV>), grid, dim3(256), 0, stream,      \
                      (const short*)q.data_ptr(), (const void*)kcache.data_ptr(),      \
                      (const void*)vcache.data_ptr(), ksp, vsp, (short*)o.data_ptr(),  \
-                     (int)Hq, (int)Hkv, (int)s, (int)pos, (int)T_alloc, scale)
+                     (int)Hq, (int)Hkv, (int)s, (int)pos, (int)T_alloc, scale,        \
+                     lens_p)
   if (HD == 128 && !quant)
     PREFILL_LAUNCH(128, false);
   else if (HD == 128)
@@ -251,4 +272,20 @@ torch::Tensor attn_prefill_fp8(torch::Tensor q, torch::Tensor kcache,
                                torch::Tensor vcache, torch::Tensor kscale,
                                torch::Tensor vscale, long pos) {
   return attn_prefill_impl(q, kcache, vcache, &kscale, &vscale, pos);
+}
+
+// Right-padded batches: seq_lens int32 [B] on the device gives each
+// sequence's valid length (clamped to [0, pos + s]). Rows and tiles past it
+// are skipped, kv rows past it are never read, and output rows past it are
+// exact zeros.
+torch::Tensor attn_prefill_varlen(torch::Tensor q, torch::Tensor kcache,
+                                  torch::Tensor vcache, long pos, torch::Tensor seq_lens) {
+  return attn_prefill_impl(q, kcache, vcache, nullptr, nullptr, pos, &seq_lens);
+}
+
+torch::Tensor attn_prefill_varlen_fp8(torch::Tensor q, torch::Tensor kcache,
+                                      torch::Tensor vcache, torch::Tensor kscale,
+                                      torch::Tensor vscale, long pos,
+                                      torch::Tensor seq_lens) {
+  return attn_prefill_impl(q, kcache, vcache, &kscale, &vscale, pos, &seq_lens);
 }

@@ -13,6 +13,10 @@ The HIP extension ABI (hypha_amd._C):
   attn_decode(q, kcache, vcache, t) -> o                   # + _fp8 / _graph
   attn_prefill(q, kcache, vcache, pos) -> o                # q bshd, any s >= 1
   attn_prefill_fp8(q, kcache, vcache, kscale, vscale, pos) -> o
+  attn_decode_varlen(q, kcache, vcache, lens_i32, max_len) -> o   # + _fp8
+  attn_prefill_varlen(q, kcache, vcache, pos, seq_lens_i32) -> o  # + _fp8
+  kv_append_fp8_(k, v, k8, v8, kscale, vscale, pos_i64[1])
+  kv_append_rows_(k, v, kcache, vcache, kscale?, vscale?, pos_i64[B])
   adamw_step_(master, param, grad, m, v, lr, b1, b2, eps, wd, step)
   adamw8_step_(master, param, grad, m8, v8, m_scale, v_scale, ...)  # 8-bit state
   nesterov_step_(master, delta_bf16, momentum, lr, mu)
@@ -128,6 +132,30 @@ def apply_rope_qk(q, k, cos, sin, layout: str = "bhsd"):
         ko = reference.apply_rope(k.transpose(1, 2), cos, sin).transpose(1, 2)
         return qo, ko
     return reference.apply_rope(q, cos, sin), reference.apply_rope(k, cos, sin)
+
+
+def apply_rope_qk_at(q, k, cos, sin, positions):
+    """Single-token RoPE at one position per sequence (ragged decode).
+
+    q [B, 1, Hq, D], k [B, 1, Hkv, D] (bshd); positions int64 [B] on q's
+    device; cos/sin [S_max, D/2] fp32. Row b is rotated with table row
+    positions[b]. The batch is viewed as ONE sequence of B tokens against the
+    gathered tables, so the existing kernel (position = token index) serves
+    unchanged. Inference only (no autograd)."""
+    if q.shape[1] != 1 or k.shape[1] != 1 or positions.shape != (q.shape[0],):
+        raise ValueError("apply_rope_qk_at: q/k must be [B, 1, H, D] and "
+                         "positions [B]")
+    cos_b = cos.index_select(0, positions)  # [B, D/2]
+    sin_b = sin.index_select(0, positions)
+    q1 = q.reshape(1, *q.shape[:1], *q.shape[2:])  # [1, B, Hq, D]
+    k1 = k.reshape(1, *k.shape[:1], *k.shape[2:])
+    if use_native(q):
+        qo, ko = _c().rope_fwd_ex(q1.contiguous(), k1.contiguous(), cos_b, sin_b,
+                                  False, "bshd")
+    else:
+        qo = reference.apply_rope(q1.transpose(1, 2), cos_b, sin_b).transpose(1, 2)
+        ko = reference.apply_rope(k1.transpose(1, 2), cos_b, sin_b).transpose(1, 2)
+    return qo.reshape(q.shape), ko.reshape(k.shape)
 
 
 # ---------------------------------------------------------------------------
@@ -277,12 +305,53 @@ def attn_decode(q, kcache, vcache, t: int, kscale=None, vscale=None) -> torch.Te
     return o.to(q.dtype)
 
 
+def attn_decode_varlen(q, kcache, vcache, lens, kscale=None, vscale=None,
+                       max_len: int | None = None) -> torch.Tensor:
+    """Single-token attention with one cache length per sequence.
+
+    q [B, Hq, D] bf16; caches as in attn_decode; lens int32 [B] on q's device,
+    lens[b] = valid rows of sequence b INCLUDING the current token (clamped to
+    [0, T_alloc]). The kernel reads the lengths at kernel time, so the call is
+    graph-capturable as is. lens[b] == 0 returns exact zeros for sequence b
+    and reads none of its cache (a finished sequence). max_len (host int,
+    default T_alloc) is an upper bound of lens that only sizes the split
+    grid. Returns [B, Hq, D] in q's dtype.
+    """
+    if lens.dtype != torch.int32 or lens.shape != (q.shape[0],):
+        raise ValueError("attn_decode_varlen: lens must be int32 [B]")
+    t_alloc = kcache.shape[1]
+    if max_len is None:
+        max_len = t_alloc
+    if not 1 <= max_len <= t_alloc:
+        raise ValueError(f"attn_decode_varlen: max_len={max_len} outside "
+                         f"[1, {t_alloc}]")
+    quant = kcache.dtype == torch.float8_e4m3fn
+    if quant and (kscale is None or vscale is None):
+        raise ValueError("attn_decode_varlen: an fp8 cache needs kscale and vscale")
+    if use_native(q) and q.shape[-1] in (64, 128) and q.shape[1] <= 8 * kcache.shape[2]:
+        if quant:
+            return _c().attn_decode_varlen_fp8(q, kcache, vcache, kscale, vscale,
+                                               lens, max_len)
+        return _c().attn_decode_varlen(q, kcache, vcache, lens, max_len)
+    # reference path: the single-length reference, one sequence at a time
+    out = torch.zeros_like(q)
+    for b, t in enumerate(lens.clamp(0, t_alloc).tolist()):
+        if t == 0:
+            continue
+        sl = slice(b, b + 1)
+        out[sl] = attn_decode(q[sl], kcache[sl], vcache[sl], t,
+                              kscale[sl] if quant else None,
+                              vscale[sl] if quant else None)
+    return out
+
+
 # ---------------------------------------------------------------------------
 # KV-cache prefill attention (ragged prompts, chunked continuation)
 # ---------------------------------------------------------------------------
 
 
-def attn_prefill(q, kcache, vcache, pos: int, kscale=None, vscale=None) -> torch.Tensor:
+def attn_prefill(q, kcache, vcache, pos: int, kscale=None, vscale=None,
+                 seq_lens=None) -> torch.Tensor:
     """Multi-token attention of one prompt chunk over an appended KV cache.
 
     q [B, s, Hq, D] (bshd), any s >= 1, row i at absolute position pos + i;
@@ -292,6 +361,11 @@ def attn_prefill(q, kcache, vcache, pos: int, kscale=None, vscale=None) -> torch
     Returns [B, s, Hq, D] in q's dtype. Native MFMA kernel
     (ops/hip/prefill.hip) on GPU for head dims 64/128; fp32 reference
     otherwise. Inference only (no autograd).
+
+    seq_lens (int32 [B] on q's device; right-padded batches): sequence b is
+    valid for len_b = clamp(seq_lens[b], 0, pos + s) rows. kv rows >= len_b
+    are masked (and never read by the kernel), q rows at positions >= len_b
+    are skipped and their output rows are exact zeros.
     """
     s = q.shape[1]
     t = pos + s
@@ -302,8 +376,18 @@ def attn_prefill(q, kcache, vcache, pos: int, kscale=None, vscale=None) -> torch
     quant = kcache.dtype == torch.float8_e4m3fn
     if quant and (kscale is None or vscale is None):
         raise ValueError("attn_prefill: an fp8 cache needs kscale and vscale")
-    if (use_native(q) and q.shape[-1] in (64, 128)
-            and q.shape[2] % kcache.shape[2] == 0):
+    if seq_lens is not None and (seq_lens.dtype != torch.int32
+                                 or seq_lens.shape != (q.shape[0],)):
+        raise ValueError("attn_prefill: seq_lens must be int32 [B]")
+    native = (use_native(q) and q.shape[-1] in (64, 128)
+              and q.shape[2] % kcache.shape[2] == 0)
+    if native and seq_lens is not None:
+        if quant:
+            return _c().attn_prefill_varlen_fp8(q.contiguous(), kcache, vcache,
+                                                kscale, vscale, pos, seq_lens)
+        return _c().attn_prefill_varlen(q.contiguous(), kcache, vcache, pos,
+                                        seq_lens)
+    if native:
         if quant:
             return _c().attn_prefill_fp8(q.contiguous(), kcache, vcache, kscale,
                                          vscale, pos)
@@ -314,7 +398,35 @@ def attn_prefill(q, kcache, vcache, pos: int, kscale=None, vscale=None) -> torch
         vc = (vcache[:, :t].float() * vscale[:, :t].unsqueeze(-1)).bfloat16()
     else:
         kc, vc = kcache[:, :t], vcache[:, :t]
-    return reference.attention_cached(q, kc, vc, pos)
+    if seq_lens is None:
+        return reference.attention_cached(q, kc, vc, pos)
+    return _attention_cached_varlen(q, kc, vc, pos, seq_lens)
+
+
+def _attention_cached_varlen(q, k, v, pos: int, seq_lens) -> torch.Tensor:
+    """reference.attention_cached with a second mask: kv j is visible to q
+    row i of sequence b iff j <= pos + i and j < len_b; rows with
+    pos + i >= len_b come out as exact zeros. Masked kv rows are zeroed
+    before the matmuls so a non-finite cache tail cannot reach the output."""
+    s, d = q.shape[1], q.shape[3]
+    t = k.shape[1]
+    rep = q.shape[2] // k.shape[2]
+    lens = seq_lens.to(torch.long).clamp(0, t)[:, None]  # [B, 1]
+    j = torch.arange(t, device=q.device)[None, :]
+    i = pos + torch.arange(s, device=q.device)[None, :]
+    kv_dead = j >= lens  # [B, t]
+    q_dead = i >= lens   # [B, s]
+    kh = k.float().masked_fill(kv_dead[:, :, None, None], 0.0).transpose(1, 2)
+    vh = v.float().masked_fill(kv_dead[:, :, None, None], 0.0).transpose(1, 2)
+    if rep != 1:
+        kh = kh.repeat_interleave(rep, dim=1)
+        vh = vh.repeat_interleave(rep, dim=1)
+    scores = (q.float().transpose(1, 2) @ kh.transpose(-1, -2)) / (d ** 0.5)
+    mask = (j[0][None, :] > i[0][:, None])[None] | kv_dead[:, None, :]  # [B, s, t]
+    mask = mask & ~q_dead[:, :, None]  # dead rows: keep the softmax finite
+    p = torch.softmax(scores.masked_fill(mask[:, None], float("-inf")), dim=-1)
+    o = (p @ vh).masked_fill(q_dead[:, None, :, None], 0.0)
+    return o.to(q.dtype).transpose(1, 2)
 
 
 def linear_skinny(x2d: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:

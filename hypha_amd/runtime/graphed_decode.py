@@ -14,6 +14,13 @@ and replayed per token with zero host round-trips:
   index_copy_ with the same index; the sampled token is written back into
   the graph's own input buffer, so replays chain with no synchronization.
 
+Ragged batches (prompt_lens) and stop tokens (eos_token_id) run a SECOND,
+lazily captured graph: the per-sequence cache lengths, the alive mask and the
+stop/pad ids are device state, every position-dependent op takes them per
+sequence (ops.apply_rope_qk_at, KVCache.append_rows, ops.attn_decode_varlen),
+and a finished sequence parks its append out of range and attends over zero
+rows. The uniform graph above is not touched by it.
+
 Greedy only — temperature sampling stays on the eager path.
 """
 
@@ -23,6 +30,7 @@ import torch
 
 from hypha_amd import ops
 from hypha_amd.models.kv_cache import KVCache
+from hypha_amd.models.llama import RaggedStep, check_prompt_lens, prefill_ragged
 
 
 class GraphedDecoder:
@@ -49,6 +57,15 @@ class GraphedDecoder:
         self.step = torch.zeros(1, dtype=torch.long, device=dev)
         self.out = torch.zeros(batch, max_new, dtype=torch.long, device=dev)
         self.graph = None
+        # ragged / stop-token state (second graph, captured on first use)
+        self.t_alloc = t_alloc
+        self.n_cache = torch.zeros(batch, dtype=torch.long, device=dev)
+        self.alive = torch.ones(batch, dtype=torch.bool, device=dev)
+        self.lens_out = torch.zeros(batch, dtype=torch.long, device=dev)
+        self.tokens_r = torch.zeros(batch, t_alloc, dtype=torch.long, device=dev)
+        self.eos_t = torch.full((1,), -1, dtype=torch.long, device=dev)  # -1: none
+        self.pad_t = torch.zeros(1, dtype=torch.long, device=dev)
+        self.graph_r = None
 
     def _step(self) -> None:
         """One decode step over static device state (graph-capturable).
@@ -96,14 +113,94 @@ class GraphedDecoder:
         self.t32 += 1
         self.step += 1
 
+    def _emit(self, x) -> None:
+        """Ragged bookkeeping after a forward (graph-capturable): sample from
+        hidden rows x [b, 1, h], write each live sequence's token directly
+        after what it has, freeze the ones that emitted the stop token, and
+        set the next input token."""
+        m = self.model
+        x = m.norm(x)
+        head_w = m.lm_head.weight if m.lm_head is not None else m.embed.weight
+        nxt = (x[:, 0] @ head_w.t()).argmax(-1, keepdim=True)  # [b, 1]
+        live = self.alive[:, None]
+        at = self.n_cache.clamp(max=self.t_alloc - 1)[:, None]
+        self.tokens_r.scatter_(1, at, torch.where(live, nxt, self.tokens_r.gather(1, at)))
+        self.lens_out.copy_(torch.where(self.alive, self.n_cache + 1, self.lens_out))
+        self.alive.logical_and_(nxt[:, 0] != self.eos_t)
+        self.tok.copy_(torch.where(self.alive[:, None], nxt, self.pad_t.expand_as(nxt)))
+
+    def _step_ragged(self) -> None:
+        """One ragged decode step over static device state (graph-capturable):
+        sequence b's current token sits at position n_cache[b]."""
+        m = self.model
+        step = RaggedStep(self.n_cache, self.alive, self.t_alloc, m.rope_cos.shape[0])
+        x = m.embed(self.tok)
+        for blk, cache in zip(m.blocks, self.caches):
+            x = blk(x, m.rope_cos, m.rope_sin, cache=cache, ragged=step)
+        self.n_cache += self.alive.to(torch.long)
+        self._emit(x)
+
+    def _generate_ragged(self, input_ids, max_new_tokens, prefill_chunk,
+                         prompt_lens, eos_token_id, pad_token_id):
+        m = self.model
+        b, s = input_ids.shape
+        if s + max_new_tokens > self.t_alloc:
+            raise ValueError(f"{s} + {max_new_tokens} tokens exceed the decoder's "
+                             f"cache of {self.t_alloc} rows")
+        lens = check_prompt_lens([s] * b if prompt_lens is None else prompt_lens,
+                                 b, s, self.dev)
+        total = s + max_new_tokens
+        self.tokens_r.fill_(pad_token_id)
+        in_prompt = torch.arange(s, device=self.dev)[None, :] < lens[:, None]
+        self.tokens_r[:, :s] = torch.where(in_prompt, input_ids, self.tokens_r[:, :s])
+        self.n_cache.copy_(lens)
+        self.lens_out.copy_(lens)
+        self.alive.fill_(True)
+        self.eos_t.fill_(-1 if eos_token_id is None else eos_token_id)
+        self.pad_t.fill_(pad_token_id)
+        if max_new_tokens > 0:
+            self._emit(prefill_ragged(m, self.caches, input_ids, lens, prefill_chunk))
+        n_replay = max_new_tokens - 1
+        if n_replay > 0 and self.graph_r is None:
+            if max_new_tokens < 8:  # not worth capturing: run eagerly
+                for _ in range(n_replay):
+                    self._step_ragged()
+                n_replay = 0
+            else:
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    self._step_ragged()
+                    self._step_ragged()
+                torch.cuda.current_stream().wait_stream(side)
+                n_replay -= 2
+                self.graph_r = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph_r):
+                    self._step_ragged()  # recorded, not executed
+        for _ in range(max(0, n_replay)):
+            self.graph_r.replay()
+        tokens = self.tokens_r[:, :total].clone()
+        return (tokens, self.lens_out.clone()) if prompt_lens is not None else tokens
+
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int,
-                 prefill_chunk: int | None = None) -> torch.Tensor:
+                 prefill_chunk: int | None = None, prompt_lens=None,
+                 eos_token_id: int | None = None, pad_token_id: int = 0):
+        """prompt_lens / eos_token_id / pad_token_id as in
+        LlamaForCausalLM.generate: with prompt_lens the batch is right-padded
+        and the call returns (tokens, lens). The ragged path always runs
+        max_new_tokens steps (no host round trip to see that all finished)."""
         m = self.model
         b, s = input_ids.shape
         assert b == self.batch and max_new_tokens <= self.max_new
         if prefill_chunk is not None and prefill_chunk < 1:
             raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
+        if prompt_lens is not None or eos_token_id is not None:
+            m.eval()
+            for cache in self.caches:
+                cache.t = 0
+            return self._generate_ragged(input_ids, max_new_tokens, prefill_chunk,
+                                         prompt_lens, eos_token_id, pad_token_id)
         m.eval()
         for cache in self.caches:  # reuse across generate() calls
             cache.t = 0

@@ -12,12 +12,19 @@ so the scheduler's FSM and lease machinery apply unchanged.
 Job config: {"model", "data": <fetch ref>, "results": <send ref>?,
              "max_new_tokens", "batch_size", "seq_len", "temperature",
              "top_k", "num_batches", "kv_cache": "fp8"?,
-             "prefill_chunk": <int>?}
+             "prefill_chunk": <int>?, "pad_token_id": <int>?,
+             "eos_token_id": <int>?}
 
 Greedy Llama-family jobs on GPU decode through the hipGraph-captured step
 (runtime/graphed_decode.py); "kv_cache": "fp8" halves KV memory;
 "prefill_chunk" feeds each prompt in pieces of at most that many tokens
 (activation memory bounded by the chunk; absent = one pass).
+
+"pad_token_id" makes every batch RAGGED: prompts are right-padded rows, a
+prompt's length is its row without the trailing run of that id (at least one
+token is kept), each sequence continues directly after its own prompt, and
+the completion file gains a "lens" tensor (final valid length per sequence)
+next to "tokens". "eos_token_id" stops a sequence at that token.
 """
 
 from __future__ import annotations
@@ -28,6 +35,15 @@ import os
 import sys
 
 import torch
+
+
+def prompt_lengths(prompts: torch.Tensor, pad_token_id: int) -> torch.Tensor:
+    """Length of each right-padded row [B, s] without its trailing run of
+    pad_token_id; at least 1 (an all-pad row keeps its first token)."""
+    s = prompts.shape[1]
+    not_pad = prompts != pad_token_id
+    last = torch.where(not_pad, torch.arange(1, s + 1, device=prompts.device), 0)
+    return last.amax(dim=1).clamp(min=1)
 
 
 def main() -> int:
@@ -79,6 +95,13 @@ def main() -> int:
         prefill_chunk = int(prefill_chunk)
         if prefill_chunk < 1:
             raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
+    pad_id = cfg.get("pad_token_id")
+    eos_id = cfg.get("eos_token_id")
+    ragged_kw = {}
+    if eos_id is not None:
+        ragged_kw["eos_token_id"] = int(eos_id)
+    if pad_id is not None:
+        ragged_kw["pad_token_id"] = int(pad_id)
 
     # greedy Llama-family serving on GPU: hipGraph-captured decode step
     # (runtime/graphed_decode.py; eager decode is launch-bound)
@@ -102,15 +125,23 @@ def main() -> int:
                 if done_batches >= num_batches:
                     break
                 prompts = ids[i : i + batch_size, :seq_len].to(device)
+                kw = dict(ragged_kw)
+                if pad_id is not None:
+                    kw["prompt_lens"] = prompt_lengths(prompts, int(pad_id))
                 if graphed is not None and prompts.shape[0] == batch_size:
                     out = graphed.generate(prompts, max_new_tokens=max_new,
-                                           prefill_chunk=prefill_chunk)
+                                           prefill_chunk=prefill_chunk, **kw)
                 else:
                     out = model.generate(prompts, max_new_tokens=max_new,
                                          temperature=temperature, top_k=top_k,
-                                         seed=0, prefill_chunk=prefill_chunk)
+                                         seed=0, prefill_chunk=prefill_chunk, **kw)
+                result = {}
+                if pad_id is not None:
+                    out, lens = out
+                    result["lens"] = lens.cpu().contiguous()
+                result["tokens"] = out.cpu().contiguous()
                 fname = f"completion-{out_idx:05d}.safetensors"
-                save_file({"tokens": out.cpu().contiguous()},
+                save_file(result,
                           os.path.join(args.work_dir, fname))
                 out_idx += 1
                 if cfg.get("results"):

@@ -33,6 +33,11 @@ def main():
                    help="hipGraph-captured decode step (greedy)")
     p.add_argument("--kv-fp8", action="store_true",
                    help="fp8 (e4m3 + per-row scales) KV cache")
+    p.add_argument("--ragged", metavar="LO:HI", default=None,
+                   help="right-padded batch: prompt lengths drawn uniformly "
+                        "from [LO, HI] (fixed seed, HI <= --prefill), generated "
+                        "through the per-sequence-length path; LO == HI runs a "
+                        "uniform batch through that path")
     args = p.parse_args()
 
     from hypha_amd import models
@@ -62,6 +67,19 @@ def main():
 
         gen = functools.partial(model.generate, kv_quant=kvq)
 
+    tag = ""
+    if args.ragged is not None:
+        import functools
+
+        lo, hi = (int(x) for x in args.ragged.split(":"))
+        if not 1 <= lo <= hi <= args.prefill:
+            raise SystemExit(f"--ragged {args.ragged}: need 1 <= LO <= HI <= --prefill")
+        g = torch.Generator().manual_seed(0)
+        lens = torch.randint(lo, hi + 1, (args.batch,), generator=g)
+        gen = functools.partial(gen, prompt_lens=lens)
+        tag = (f" ragged {lo}:{hi} (mean {lens.float().mean().item():.0f}, "
+               f"max {int(lens.max())})")
+
     # warm (weights/algos/graph capture), then difference two WARM runs so
     # one-time costs never land in the per-token figure
     gen(ids, max_new_tokens=args.warmup)
@@ -76,7 +94,10 @@ def main():
     t_long = time.perf_counter() - t0
     dt = t_long - t_short
     toks = args.batch * args.decode
-    print(f"{args.model} b{args.batch} prefill{args.prefill}: "
+    if args.ragged is not None:
+        out, out_lens = out
+        assert out_lens.tolist() == (lens + args.decode + args.warmup).tolist()
+    print(f"{args.model} b{args.batch} prefill{args.prefill}{tag}: "
           f"{toks / dt:.0f} decode tok/s  ({dt / args.decode * 1e3:.2f} ms/step)"
           f"  [prefill+{args.warmup}: {t_short:.2f}s]")
     assert out.shape[1] == args.prefill + args.decode + args.warmup
