@@ -405,6 +405,9 @@ int main(int argc, char** argv) {
       inf["num_batches"] = cfg.get_or("num_batches", Json((int64_t)2));
       if (cfg.has("temperature")) inf["temperature"] = cfg.at("temperature");
       if (cfg.has("top_k")) inf["top_k"] = cfg.at("top_k");
+      if (cfg.has("top_p")) inf["top_p"] = cfg.at("top_p");
+      if (cfg.has("sampler")) inf["sampler"] = cfg.at("sampler");
+      if (cfg.has("seed")) inf["seed"] = cfg.at("seed");
       Json ex;
       ex["infer"] = inf;
       Json job;

@@ -295,9 +295,28 @@ def _sample(logits, temperature, top_k, gen):
     return torch.multinomial(probs, 1, generator=gen)
 
 
+def check_sampler(sampler, temperature, top_p, seed) -> None:
+    if sampler not in ("multinomial", "philox"):
+        raise ValueError(f"sampler must be 'multinomial' or 'philox', got {sampler!r}")
+    if sampler == "multinomial":
+        if top_p != 1.0:
+            raise ValueError("top_p < 1 needs sampler='philox'")
+        return
+    if seed is None or not temperature > 0:
+        raise ValueError("sampler='philox' needs a seed and temperature > 0")
+    if not 0 < top_p <= 1:
+        raise ValueError(f"top_p must lie in (0, 1], got {top_p}")
+
+
+def _sample_philox(logits, temperature, top_k, top_p, seed, i):
+    """The i-th new token of every row: u = philox_uniform(seed, i, B)."""
+    u = ops.philox_uniform(seed, i, logits.shape[0], device=logits.device)
+    return ops.sample_token(logits, u, temperature, top_k, top_p)
+
+
 def _generate_ragged(self, input_ids, max_new_tokens, temperature, top_k, seed,
                      kv_quant, prefill_chunk, prompt_lens, eos_token_id,
-                     pad_token_id):
+                     pad_token_id, top_p=1.0, sampler="multinomial"):
     """Generation over a right-padded batch and/or with a stop token.
     Returns (tokens [B, s + max_new_tokens], lens [B])."""
     from .kv_cache import KVCache
@@ -329,7 +348,10 @@ def _generate_ragged(self, input_ids, max_new_tokens, temperature, top_k, seed,
             logits = self.lm_head(x)[:, 0]
         else:
             logits = torch.nn.functional.linear(x, self.embed.weight)[:, 0]
-        nxt = _sample(logits, temperature, top_k, gen)  # [B, 1]
+        if sampler == "philox":
+            nxt = _sample_philox(logits, temperature, top_k, top_p, seed, i)
+        else:
+            nxt = _sample(logits, temperature, top_k, gen)  # [B, 1]
         # a live sequence's new token goes directly after what it has
         at = n_cache.clamp(max=total - 1)[:, None]
         tokens.scatter_(1, at, torch.where(alive[:, None], nxt, tokens.gather(1, at)))
@@ -354,7 +376,8 @@ def _generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
               temperature: float = 0.0, top_k: int = 0,
               seed: int | None = None, kv_quant: str | None = None,
               prefill_chunk: int | None = None, prompt_lens=None,
-              eos_token_id: int | None = None, pad_token_id: int = 0):
+              eos_token_id: int | None = None, pad_token_id: int = 0,
+              top_p: float = 1.0, sampler: str = "multinomial"):
     """Autoregressive generation with a per-layer KV cache (inference parity:
     the reference serves inference through the same executor surface).
     prefill_chunk feeds the prompt in pieces of at most that many tokens
@@ -366,15 +389,23 @@ def _generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
     new tokens directly after its own prompt, pad_token_id everywhere else,
     lens[b] its final valid length. eos_token_id stops a sequence once it
     emits that token (kept; pads after it); without prompt_lens the call then
-    still returns only tokens."""
+    still returns only tokens.
+
+    sampler="multinomial" (default) draws with torch.multinomial from a
+    torch.Generator. sampler="philox" (needs seed and temperature > 0) draws
+    the i-th new token of row b from u = ops.philox_uniform(seed, i, B)[b]
+    through ops.sample_token, which also provides nucleus sampling (top_p):
+    the output is a function of (model, prompt, seed, parameters) alone, the
+    same in the graphed decoder."""
     from .kv_cache import KVCache
 
+    check_sampler(sampler, temperature, top_p, seed)
     if prefill_chunk is not None and prefill_chunk < 1:
         raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
     if prompt_lens is not None or eos_token_id is not None:
         tokens, lens = _generate_ragged(
             self, input_ids, max_new_tokens, temperature, top_k, seed, kv_quant,
-            prefill_chunk, prompt_lens, eos_token_id, pad_token_id)
+            prefill_chunk, prompt_lens, eos_token_id, pad_token_id, top_p, sampler)
         return (tokens, lens) if prompt_lens is not None else tokens
     self.eval()
     b, s = input_ids.shape
@@ -403,14 +434,17 @@ def _generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
         run_blocks(x_in[:, :prefill_chunk], pos)
         pos += prefill_chunk
         x_in = x_in[:, prefill_chunk:]
-    for _ in range(max_new_tokens):
+    for i in range(max_new_tokens):
         x = run_blocks(x_in, pos)
         x = self.norm(x[:, -1:])
         if self.lm_head is not None:
             logits = self.lm_head(x)[:, 0]
         else:
             logits = torch.nn.functional.linear(x, self.embed.weight)[:, 0]
-        nxt = _sample(logits, temperature, top_k, gen)
+        if sampler == "philox":
+            nxt = _sample_philox(logits, temperature, top_k, top_p, seed, i)
+        else:
+            nxt = _sample(logits, temperature, top_k, gen)
         pos += x_in.shape[1]
         tokens = torch.cat([tokens, nxt], dim=1)
         x_in = nxt

@@ -66,7 +66,9 @@ from .interface import (  # noqa: E402
     gelu,
     layernorm,
     linear_skinny,
+    philox_uniform,
     rmsnorm,
+    sample_token,
     swiglu,
 )
 
@@ -91,4 +93,6 @@ __all__ = [
     "fused_nesterov",
     "linear_skinny",
     "extract_delta",
+    "sample_token",
+    "philox_uniform",
 ]

@@ -128,6 +128,10 @@ torch::Tensor attn_prefill_fp8(torch::Tensor q, torch::Tensor kcache,
                                torch::Tensor vscale, long pos);
 // skinny_gemm.hip (decode GEMV, M <= 8)
 torch::Tensor skinny_gemm(torch::Tensor x, torch::Tensor w);
+// sample.hip (temperature / top-k / top-p sampling, Philox uniforms)
+torch::Tensor sample_token(torch::Tensor logits, torch::Tensor u, torch::Tensor temperature,
+                           torch::Tensor top_k, torch::Tensor top_p);
+torch::Tensor philox_uniform(torch::Tensor seed, torch::Tensor step, long n);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adamw_step_", &adamw_step_);
@@ -182,4 +186,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_prefill_varlen", &attn_prefill_varlen);
   m.def("attn_prefill_varlen_fp8", &attn_prefill_varlen_fp8);
   m.def("skinny_gemm", &skinny_gemm);
+  m.def("sample_token", &sample_token);
+  m.def("philox_uniform", &philox_uniform);
 }

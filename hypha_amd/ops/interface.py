@@ -22,6 +22,8 @@ The HIP extension ABI (hypha_amd._C):
   nesterov_step_(master, delta_bf16, momentum, lr, mu)
   extract_delta(master, theta0, out_bf16)
   grad_norm_sq(flat_bf16) -> fp32 scalar
+  sample_token(logits_bf16, u_f32, temp_f32[1], top_k_i32[1], top_p_f32[1]) -> int64 [B, 1]
+  philox_uniform(seed_i64[1], step_i64[1], n) -> fp32 [n]
 """
 
 from __future__ import annotations
@@ -437,6 +439,65 @@ def linear_skinny(x2d: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
             and weight.dtype == torch.bfloat16):
         return _c().skinny_gemm(x2d.contiguous(), weight)
     return x2d @ weight.t()
+
+
+# ---------------------------------------------------------------------------
+# Token sampling (temperature / top-k / top-p) and its Philox uniforms
+# ---------------------------------------------------------------------------
+
+
+def _dev_scalar(x, dtype, device) -> torch.Tensor:
+    """A Python number or a 1-element tensor -> 1-element tensor on device
+    (no host round trip for a tensor already there)."""
+    if isinstance(x, torch.Tensor):
+        return x.reshape(1).to(device=device, dtype=dtype)
+    return torch.tensor([x], dtype=dtype, device=device)
+
+
+@torch.no_grad()
+def sample_token(logits: torch.Tensor, u: torch.Tensor, temperature, top_k=0,
+                 top_p=1.0) -> torch.Tensor:
+    """One token per row: logits [B, V], u fp32 [B] in [0, 1) -> int64 [B, 1].
+
+    A pure function of (logits, u), the same on CPU and GPU (contract:
+    reference.sample_token): rank by logit descending, ties by index
+    ascending; top_k keeps the first k (0 or >= V: off); top_p in (0, 1] then
+    keeps the shortest prefix reaching that share of the kept mass; u picks by
+    inverse CDF. temperature > 0 (greedy is the caller's argmax). The three
+    parameters may be Python numbers (validated: ValueError) or 1-element
+    device tensors (read by the kernel at kernel time, so a captured graph
+    serves every setting). Native kernel (ops/hip/sample.hip) for contiguous
+    bf16 GPU logits; the reference for everything else."""
+    reference.check_sampling_params(temperature, top_k, top_p)
+    if not isinstance(top_k, torch.Tensor):
+        top_k = min(int(top_k), 2 ** 31 - 1)
+    if logits.dim() != 2 or u.numel() != logits.shape[0]:
+        raise ValueError("sample_token: logits must be [B, V] and u [B]")
+    if (logits.dtype == torch.bfloat16 and logits.is_contiguous()
+            and use_native(logits)):
+        dev = logits.device
+        return _c().sample_token(
+            logits, u.reshape(-1).to(device=dev, dtype=torch.float32).contiguous(),
+            _dev_scalar(temperature, torch.float32, dev),
+            _dev_scalar(top_k, torch.int32, dev),
+            _dev_scalar(top_p, torch.float32, dev))
+    return reference.sample_token(logits, u, temperature, top_k, top_p)
+
+
+@torch.no_grad()
+def philox_uniform(seed, step, n: int, device=None) -> torch.Tensor:
+    """fp32 [n] uniforms in [0, 1): row r of Philox4x32-10 with key
+    (seed & 0xffffffff, seed >> 32) and counter (r, step & 0xffffffff,
+    step >> 32, 0), u = (x0 >> 8) * 2**-24. seed and step are ints or
+    1-element int64 tensors; device defaults to theirs (else the CPU)."""
+    if device is None:
+        device = next((x.device for x in (seed, step)
+                       if isinstance(x, torch.Tensor)), torch.device("cpu"))
+    device = torch.device(device)
+    if device.type == "cuda" and use_native(torch.empty(0, device=device)):
+        return _c().philox_uniform(_dev_scalar(seed, torch.long, device),
+                                   _dev_scalar(step, torch.long, device), int(n))
+    return reference.philox_uniform(seed, step, n, device=device)
 
 
 # ---------------------------------------------------------------------------

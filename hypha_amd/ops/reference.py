@@ -195,3 +195,105 @@ def nesterov_outer_step(
 def extract_delta(theta_t: torch.Tensor, theta_0: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     torch.sub(theta_t, theta_0, out=out)
     return out
+
+
+# ---------------------------------------------------------------------------
+# Token sampling: counter-based Philox4x32-10 uniforms and one deterministic
+# function (logits, u) -> token (temperature, top-k, top-p). The HIP kernel
+# (ops/hip/sample.hip) computes the same function.
+# ---------------------------------------------------------------------------
+
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_M32 = 0xFFFFFFFF
+
+
+def _mulhilo32(a: torch.Tensor, m: int):
+    """(hi, lo) 32-bit halves of a * m; a int64 holding 32-bit values. 16-bit
+    limbs keep every intermediate below 2**63."""
+    a0, a1 = a & 0xFFFF, a >> 16
+    m0, m1 = m & 0xFFFF, m >> 16
+    mid = a1 * m0 + a0 * m1
+    low = a0 * m0 + ((mid & 0xFFFF) << 16)
+    return (a1 * m1 + (mid >> 16) + (low >> 32)) & _M32, low & _M32
+
+
+def philox4x32(counter: torch.Tensor, key: torch.Tensor) -> torch.Tensor:
+    """Philox4x32-10. counter int64 [..., 4], key int64 [..., 2] (32-bit
+    values) -> int64 [..., 4] of 32-bit outputs."""
+    c0, c1, c2, c3 = (counter[..., i] & _M32 for i in range(4))
+    k0, k1 = key[..., 0] & _M32, key[..., 1] & _M32
+    for r in range(10):
+        if r:
+            k0 = (k0 + _PHILOX_W0) & _M32
+            k1 = (k1 + _PHILOX_W1) & _M32
+        hi0, lo0 = _mulhilo32(c0, _PHILOX_M0)
+        hi1, lo1 = _mulhilo32(c2, _PHILOX_M1)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+    return torch.stack([c0, c1, c2, c3], dim=-1)
+
+
+def _scalar(x):
+    return x.item() if isinstance(x, torch.Tensor) else x
+
+
+def philox_uniform(seed, step, n: int, device=None) -> torch.Tensor:
+    """fp32 [n]: row r gets u = (x0 >> 8) * 2**-24 with x0 the first output of
+    Philox4x32-10 under key (seed & 0xffffffff, seed >> 32) and counter
+    (r, step & 0xffffffff, step >> 32, 0)."""
+    seed, step = int(_scalar(seed)), int(_scalar(step))
+    counter = torch.zeros(n, 4, dtype=torch.long)
+    counter[:, 0] = torch.arange(n)
+    counter[:, 1] = step & _M32
+    counter[:, 2] = (step >> 32) & _M32
+    key = torch.tensor([seed & _M32, (seed >> 32) & _M32], dtype=torch.long)
+    x0 = philox4x32(counter, key.expand(n, 2))[:, 0]
+    u = (x0 >> 8).to(torch.float32) * (2.0 ** -24)
+    return u if device is None else u.to(device)
+
+
+def check_sampling_params(temperature, top_k, top_p) -> None:
+    """ValueError for host-visible parameters outside the contract (device
+    tensors are not read back here)."""
+    if not isinstance(temperature, torch.Tensor) and not temperature > 0:
+        raise ValueError(f"sample_token: temperature must be > 0, got {temperature}")
+    if not isinstance(top_k, torch.Tensor) and (int(top_k) != top_k or top_k < 0):
+        raise ValueError(f"sample_token: top_k must be an int >= 0, got {top_k}")
+    if not isinstance(top_p, torch.Tensor) and not 0 < top_p <= 1:
+        raise ValueError(f"sample_token: top_p must lie in (0, 1], got {top_p}")
+
+
+def sample_token(logits: torch.Tensor, u: torch.Tensor, temperature, top_k=0,
+                 top_p=1.0) -> torch.Tensor:
+    """One token per row of logits [B, V] from the uniform u [B] in [0, 1).
+
+    Tokens are ranked by logit descending, ties by index ascending (-0.0 ==
+    +0.0). Mass m_i = exp((z_i - z_max) / temperature) in fp32 (-inf: 0).
+    top_k keeps the first k ranked tokens (0 or >= V: off); top_p then keeps
+    the shortest ranked prefix whose mass reaches top_p of the kept mass; the
+    result is the first kept token whose inclusive cumulative mass (fp64)
+    exceeds u times the kept mass, else the last kept token with mass.
+    Returns int64 [B, 1]."""
+    check_sampling_params(temperature, top_k, top_p)
+    t, k, p = float(_scalar(temperature)), int(_scalar(top_k)), float(_scalar(top_p))
+    if not t > 0 or not 0 < p <= 1:
+        raise ValueError(f"sample_token: temperature={t}, top_p={p} out of range")
+    b, v = logits.shape
+    z = logits.detach().float() + 0.0  # -0.0 -> +0.0
+    zs, idx = torch.sort(z, dim=-1, descending=True, stable=True)
+    m = torch.exp((zs - zs[:, :1]) / t)
+    m = torch.nan_to_num(m, nan=0.0).masked_fill(zs == float("-inf"), 0.0)
+    rank = torch.arange(v, device=logits.device)[None, :]
+    n_keep = torch.full((b, 1), k if 0 < k < v else v, device=logits.device)
+    c = (m * (rank < n_keep)).double().cumsum(-1)
+    if p < 1:
+        n_p = (c < p * c[:, -1:]).sum(-1, keepdim=True) + 1
+        n_keep = torch.minimum(n_keep, n_p)
+    keep = rank < n_keep
+    z_kept = c.gather(1, n_keep - 1)
+    thresh = u.detach().to(logits.device).double().reshape(b, 1) * z_kept
+    hit = keep & (c > thresh)
+    first_hit = torch.where(hit, rank, v).amin(-1, keepdim=True)
+    last_mass = torch.where(keep & (m > 0), rank, 0).amax(-1, keepdim=True)
+    j = torch.where(first_hit < v, first_hit, last_mass)
+    return idx.gather(1, j)

@@ -1,10 +1,10 @@
-"""hipGraph-captured greedy decoding for the Llama family.
+"""hipGraph-captured decoding (greedy or sampled) for the Llama family.
 
 Eager single-token decode is LAUNCH-bound (measured 6.6 ms/step at b8 for
 Llama-3-8B: ~300 kernels x ~4-6 us of launch+epilogue overhead each, while
 the GEMMs themselves need ~2 ms of HBM time). The whole per-token step —
 embed, per-layer norm/projections/RoPE/cache-append/decode-attention/MLP,
-final norm, logits, argmax, bookkeeping — is captured ONCE as a hipGraph
+final norm, logits, token choice, bookkeeping — is captured ONCE as a hipGraph
 and replayed per token with zero host round-trips:
 
 * the cache length lives in a device int32 read by the decode kernel at
@@ -21,7 +21,14 @@ sequence (ops.apply_rope_qk_at, KVCache.append_rows, ops.attn_decode_varlen),
 and a finished sequence parks its append out of range and attends over zero
 rows. The uniform graph above is not touched by it.
 
-Greedy only — temperature sampling stays on the eager path.
+Sampling (temperature > 0) has its own two lazily captured graphs, uniform
+and ragged; the greedy graphs are not touched by them. Everything a draw
+depends on is device state read at kernel time — Philox seed and step counter,
+temperature, top_k, top_p — so one capture serves every seed and setting:
+a step draws u = ops.philox_uniform(seed, step, B), picks with
+ops.sample_token (ops/hip/sample.hip), records u in u_log[:, step] and
+advances the counter inside the graph. The tokens are those of
+model.generate(sampler="philox") with the same seed and parameters.
 """
 
 from __future__ import annotations
@@ -66,8 +73,29 @@ class GraphedDecoder:
         self.eos_t = torch.full((1,), -1, dtype=torch.long, device=dev)  # -1: none
         self.pad_t = torch.zeros(1, dtype=torch.long, device=dev)
         self.graph_r = None
+        # sampling state (third and fourth graph, captured on first use)
+        self.s_seed = torch.zeros(1, dtype=torch.long, device=dev)
+        self.s_step = torch.zeros(1, dtype=torch.long, device=dev)
+        self.s_temp = torch.ones(1, dtype=torch.float32, device=dev)
+        self.s_topk = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.s_topp = torch.ones(1, dtype=torch.float32, device=dev)
+        self.u_log = torch.zeros(batch, max_new, dtype=torch.float32, device=dev)
+        self.graph_s = None
+        self.graph_rs = None
 
-    def _step(self) -> None:
+    def _pick(self, logits, sample: bool):
+        """Next token [b, 1] from logits [b, V] (graph-capturable). Sampling
+        draws this step's uniforms from the device seed/step, logs them and
+        advances the step counter."""
+        if not sample:
+            return logits.argmax(-1, keepdim=True)
+        u = ops.philox_uniform(self.s_seed, self.s_step, self.batch)
+        nxt = ops.sample_token(logits, u, self.s_temp, self.s_topk, self.s_topp)
+        self.u_log.index_copy_(1, self.s_step.clamp(max=self.max_new - 1), u[:, None])
+        self.s_step += 1
+        return nxt
+
+    def _step(self, sample: bool = False) -> None:
         """One decode step over static device state (graph-capturable).
         GEMMs run 2-D through hipBLASLt (the hand-written skinny-M GEMV,
         ops/hip/skinny_gemm.hip, measured 0.4 TB/s vs the library's 1.8-5.9
@@ -105,7 +133,7 @@ class GraphedDecoder:
         x = m.norm(x)
         head_w = m.lm_head.weight if m.lm_head is not None else m.embed.weight
         logits = lin(x[:, 0], head_w)
-        nxt = logits.argmax(-1, keepdim=True)  # [b, 1]
+        nxt = self._pick(logits, sample)  # [b, 1]
         self.step.clamp_(max=self.max_new - 1)
         self.out.index_copy_(1, self.step, nxt)
         self.tok.copy_(nxt)
@@ -113,7 +141,7 @@ class GraphedDecoder:
         self.t32 += 1
         self.step += 1
 
-    def _emit(self, x) -> None:
+    def _emit(self, x, sample: bool = False) -> None:
         """Ragged bookkeeping after a forward (graph-capturable): sample from
         hidden rows x [b, 1, h], write each live sequence's token directly
         after what it has, freeze the ones that emitted the stop token, and
@@ -121,7 +149,7 @@ class GraphedDecoder:
         m = self.model
         x = m.norm(x)
         head_w = m.lm_head.weight if m.lm_head is not None else m.embed.weight
-        nxt = (x[:, 0] @ head_w.t()).argmax(-1, keepdim=True)  # [b, 1]
+        nxt = self._pick(x[:, 0] @ head_w.t(), sample)  # [b, 1]
         live = self.alive[:, None]
         at = self.n_cache.clamp(max=self.t_alloc - 1)[:, None]
         self.tokens_r.scatter_(1, at, torch.where(live, nxt, self.tokens_r.gather(1, at)))
@@ -129,7 +157,7 @@ class GraphedDecoder:
         self.alive.logical_and_(nxt[:, 0] != self.eos_t)
         self.tok.copy_(torch.where(self.alive[:, None], nxt, self.pad_t.expand_as(nxt)))
 
-    def _step_ragged(self) -> None:
+    def _step_ragged(self, sample: bool = False) -> None:
         """One ragged decode step over static device state (graph-capturable):
         sequence b's current token sits at position n_cache[b]."""
         m = self.model
@@ -138,10 +166,10 @@ class GraphedDecoder:
         for blk, cache in zip(m.blocks, self.caches):
             x = blk(x, m.rope_cos, m.rope_sin, cache=cache, ragged=step)
         self.n_cache += self.alive.to(torch.long)
-        self._emit(x)
+        self._emit(x, sample)
 
     def _generate_ragged(self, input_ids, max_new_tokens, prefill_chunk,
-                         prompt_lens, eos_token_id, pad_token_id):
+                         prompt_lens, eos_token_id, pad_token_id, sample=False):
         m = self.model
         b, s = input_ids.shape
         if s + max_new_tokens > self.t_alloc:
@@ -159,48 +187,73 @@ class GraphedDecoder:
         self.eos_t.fill_(-1 if eos_token_id is None else eos_token_id)
         self.pad_t.fill_(pad_token_id)
         if max_new_tokens > 0:
-            self._emit(prefill_ragged(m, self.caches, input_ids, lens, prefill_chunk))
+            self._emit(prefill_ragged(m, self.caches, input_ids, lens, prefill_chunk),
+                       sample)
         n_replay = max_new_tokens - 1
-        if n_replay > 0 and self.graph_r is None:
+        graph = self.graph_rs if sample else self.graph_r
+        if n_replay > 0 and graph is None:
             if max_new_tokens < 8:  # not worth capturing: run eagerly
                 for _ in range(n_replay):
-                    self._step_ragged()
+                    self._step_ragged(sample)
                 n_replay = 0
             else:
                 side = torch.cuda.Stream()
                 side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side):
-                    self._step_ragged()
-                    self._step_ragged()
+                    self._step_ragged(sample)
+                    self._step_ragged(sample)
                 torch.cuda.current_stream().wait_stream(side)
                 n_replay -= 2
-                self.graph_r = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph_r):
-                    self._step_ragged()  # recorded, not executed
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    self._step_ragged(sample)  # recorded, not executed
+                if sample:
+                    self.graph_rs = graph
+                else:
+                    self.graph_r = graph
         for _ in range(max(0, n_replay)):
-            self.graph_r.replay()
+            graph.replay()
         tokens = self.tokens_r[:, :total].clone()
         return (tokens, self.lens_out.clone()) if prompt_lens is not None else tokens
 
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int,
                  prefill_chunk: int | None = None, prompt_lens=None,
-                 eos_token_id: int | None = None, pad_token_id: int = 0):
+                 eos_token_id: int | None = None, pad_token_id: int = 0,
+                 temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
+                 seed: int | None = None):
         """prompt_lens / eos_token_id / pad_token_id as in
         LlamaForCausalLM.generate: with prompt_lens the batch is right-padded
         and the call returns (tokens, lens). The ragged path always runs
-        max_new_tokens steps (no host round trip to see that all finished)."""
+        max_new_tokens steps (no host round trip to see that all finished).
+
+        temperature <= 0 decodes greedily. temperature > 0 samples as
+        model.generate(sampler="philox") does (needs seed; top_k 0 = off,
+        top_p in (0, 1]); u_log[:, i] then holds the uniforms of the i-th new
+        token. A finished ragged sequence still draws but stays parked."""
         m = self.model
         b, s = input_ids.shape
         assert b == self.batch and max_new_tokens <= self.max_new
         if prefill_chunk is not None and prefill_chunk < 1:
             raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
+        sample = temperature > 0
+        if sample:
+            if seed is None:
+                raise ValueError("sampling (temperature > 0) needs a seed")
+            ops.reference.check_sampling_params(temperature, top_k, top_p)
+            self.s_seed.fill_(seed)
+            self.s_step.zero_()
+            self.s_temp.fill_(temperature)
+            self.s_topk.fill_(min(int(top_k), 2 ** 31 - 1))
+            self.s_topp.fill_(top_p)
+            self.u_log.zero_()
         if prompt_lens is not None or eos_token_id is not None:
             m.eval()
             for cache in self.caches:
                 cache.t = 0
             return self._generate_ragged(input_ids, max_new_tokens, prefill_chunk,
-                                         prompt_lens, eos_token_id, pad_token_id)
+                                         prompt_lens, eos_token_id, pad_token_id,
+                                         sample)
         m.eval()
         for cache in self.caches:  # reuse across generate() calls
             cache.t = 0
@@ -214,7 +267,7 @@ class GraphedDecoder:
         xl = m.norm(x[:, -1:])
         logits = (m.lm_head(xl) if m.lm_head is not None
                   else torch.nn.functional.linear(xl, m.embed.weight))
-        g0 = logits[:, 0].argmax(-1, keepdim=True)
+        g0 = self._pick(logits[:, 0], sample)
         self.out[:, 0:1].copy_(g0)
         self.tok.copy_(g0)
         self.pos.fill_(s)
@@ -222,22 +275,27 @@ class GraphedDecoder:
         self.step.fill_(1)
 
         n_replay = max_new_tokens - 1
-        if n_replay > 0 and self.graph is None:
+        graph = self.graph_s if sample else self.graph
+        if n_replay > 0 and graph is None:
             if max_new_tokens < 8:  # not worth capturing: run eagerly
                 for _ in range(n_replay):
-                    self._step()
+                    self._step(sample)
                 return torch.cat([input_ids, self.out[:, :max_new_tokens]], dim=1)
             # 2 warmup steps on a side stream (they are REAL steps), capture
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self._step()
-                self._step()
+                self._step(sample)
+                self._step(sample)
             torch.cuda.current_stream().wait_stream(side)
             n_replay -= 2
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self._step()  # recorded, not executed
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                self._step(sample)  # recorded, not executed
+            if sample:
+                self.graph_s = graph
+            else:
+                self.graph = graph
         for _ in range(max(0, n_replay)):
-            self.graph.replay()
+            graph.replay()
         return torch.cat([input_ids, self.out[:, :max_new_tokens]], dim=1)

@@ -11,12 +11,17 @@ so the scheduler's FSM and lease machinery apply unchanged.
 
 Job config: {"model", "data": <fetch ref>, "results": <send ref>?,
              "max_new_tokens", "batch_size", "seq_len", "temperature",
-             "top_k", "num_batches", "kv_cache": "fp8"?,
+             "top_k", "top_p"?, "sampler": "philox"?, "seed"?,
+             "num_batches", "kv_cache": "fp8"?,
              "prefill_chunk": <int>?, "pad_token_id": <int>?,
              "eos_token_id": <int>?}
 
-Greedy Llama-family jobs on GPU decode through the hipGraph-captured step
-(runtime/graphed_decode.py); "kv_cache": "fp8" halves KV memory;
+Llama-family jobs on GPU decode through the hipGraph-captured step
+(runtime/graphed_decode.py) when they are greedy, or when they sample with
+"sampler": "philox" (temperature > 0; "top_k", "top_p" and "seed" apply: the
+tokens are a function of the prompt, the seed and those parameters, drawn by
+ops.sample_token from Philox uniforms). Without "sampler", a job with a
+temperature samples with torch.multinomial on the eager path. "kv_cache": "fp8" halves KV memory;
 "prefill_chunk" feeds each prompt in pieces of at most that many tokens
 (activation memory bounded by the chunk; absent = one pass).
 
@@ -90,6 +95,17 @@ def main() -> int:
     num_batches = int(cfg.get("num_batches", 1))
     temperature = float(cfg.get("temperature", 0.0))
     top_k = int(cfg.get("top_k", 0))
+    top_p = float(cfg.get("top_p", 1.0))
+    sampler = cfg.get("sampler", "multinomial")
+    philox = sampler == "philox" and temperature > 0
+    sample_kw = {}
+    if philox:
+        sample_kw = dict(temperature=temperature, top_k=top_k, top_p=top_p,
+                         seed=int(cfg.get("seed", 0)))
+    elif sampler not in ("multinomial", "philox"):
+        raise ValueError(f"unknown sampler {sampler!r}")
+    elif sampler == "multinomial" and top_p != 1.0:
+        raise ValueError('"top_p" needs "sampler": "philox"')
     prefill_chunk = cfg.get("prefill_chunk")
     if prefill_chunk is not None:
         prefill_chunk = int(prefill_chunk)
@@ -103,10 +119,10 @@ def main() -> int:
     if pad_id is not None:
         ragged_kw["pad_token_id"] = int(pad_id)
 
-    # greedy Llama-family serving on GPU: hipGraph-captured decode step
-    # (runtime/graphed_decode.py; eager decode is launch-bound)
+    # Llama-family serving on GPU, greedy or Philox-sampled: hipGraph-captured
+    # decode step (runtime/graphed_decode.py; eager decode is launch-bound)
     graphed = None
-    if (temperature <= 0 and device.type == "cuda"
+    if ((temperature <= 0 or philox) and device.type == "cuda"
             and type(model).__name__ == "LlamaForCausalLM"
             and model.cfg.head_dim in (64, 128)
             and model.cfg.n_heads // model.cfg.n_kv_heads <= 8):
@@ -130,7 +146,12 @@ def main() -> int:
                     kw["prompt_lens"] = prompt_lengths(prompts, int(pad_id))
                 if graphed is not None and prompts.shape[0] == batch_size:
                     out = graphed.generate(prompts, max_new_tokens=max_new,
-                                           prefill_chunk=prefill_chunk, **kw)
+                                           prefill_chunk=prefill_chunk, **kw,
+                                           **sample_kw)
+                elif philox:
+                    out = model.generate(prompts, max_new_tokens=max_new,
+                                         prefill_chunk=prefill_chunk,
+                                         sampler="philox", **kw, **sample_kw)
                 else:
                     out = model.generate(prompts, max_new_tokens=max_new,
                                          temperature=temperature, top_k=top_k,

@@ -30,7 +30,13 @@ def main():
     p.add_argument("--decode", type=int, default=128)
     p.add_argument("--warmup", type=int, default=16)
     p.add_argument("--graph", action="store_true",
-                   help="hipGraph-captured decode step (greedy)")
+                   help="hipGraph-captured decode step")
+    p.add_argument("--sample", metavar="T[:K[:P]]", default=None,
+                   help="sample with temperature T, top-k K (0 = off) and "
+                        "top-p P. With --graph: the graphed decoder's sampling "
+                        "graph (ops.sample_token, Philox uniforms). Without: "
+                        "the eager loop, torch.multinomial unless P is given "
+                        "(top-p needs sampler='philox')")
     p.add_argument("--kv-fp8", action="store_true",
                    help="fp8 (e4m3 + per-row scales) KV cache")
     p.add_argument("--ragged", metavar="LO:HI", default=None,
@@ -68,6 +74,20 @@ def main():
         gen = functools.partial(model.generate, kv_quant=kvq)
 
     tag = ""
+    if args.sample is not None:
+        import functools
+
+        parts = args.sample.split(":")
+        if not 1 <= len(parts) <= 3:
+            raise SystemExit(f"--sample {args.sample}: expected T[:K[:P]]")
+        kw = dict(temperature=float(parts[0]), seed=0,
+                  top_k=int(parts[1]) if len(parts) > 1 else 0)
+        if len(parts) > 2:
+            kw["top_p"] = float(parts[2])
+            if not args.graph:
+                kw["sampler"] = "philox"
+        gen = functools.partial(gen, **kw)
+        tag = f" sample {args.sample}"
     if args.ragged is not None:
         import functools
 
@@ -77,7 +97,7 @@ def main():
         g = torch.Generator().manual_seed(0)
         lens = torch.randint(lo, hi + 1, (args.batch,), generator=g)
         gen = functools.partial(gen, prompt_lens=lens)
-        tag = (f" ragged {lo}:{hi} (mean {lens.float().mean().item():.0f}, "
+        tag += (f" ragged {lo}:{hi} (mean {lens.float().mean().item():.0f}, "
                f"max {int(lens.max())})")
 
     # warm (weights/algos/graph capture), then difference two WARM runs so
