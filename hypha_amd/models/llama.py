@@ -111,6 +111,14 @@ class Attention(nn.Module):
             o = ragged.attend(q, k, v, cos, sin, cache)
             return self.wo(o.reshape(b, 1, -1))
         q, k = ops.apply_rope_qk(q, k, cos[pos:], sin[pos:], layout="bshd")
+        if hasattr(cache, "table"):
+            # paged cache (always the per-sequence route): only the rows a
+            # sequence has are written, into its own pages
+            cache.append_chunk(k, v, pos, seq_lens)
+            o = ops.attn_prefill_paged(q, cache.k, cache.v, cache.table.table, pos,
+                                       cache.k_scale, cache.v_scale,
+                                       seq_lens=seq_lens)
+            return self.wo(o.reshape(b, s, -1))
         t = cache.append(k, v)
         if seq_lens is not None:
             # right-padded batch: the pads' K/V rows are written like any
@@ -233,7 +241,9 @@ class RaggedStep:
     appends at row n_cache[b] and attends over n_cache[b] + 1 rows. A finished
     one parks its append out of range (nothing written) and attends over 0
     rows (exact zeros, no cache read). All device tensors: building one costs
-    no host round trip, so a step can be graph-captured."""
+    no host round trip, so a step can be graph-captured. t_alloc is the
+    parking position: one no append writes at (a contiguous cache's T_max, a
+    paged one's max_pages * 64)."""
 
     __slots__ = ("rope_pos", "append_pos", "attn_lens", "max_len")
 
@@ -248,6 +258,11 @@ class RaggedStep:
     def attend(self, q, k, v, cos, sin, cache):
         q, k = ops.apply_rope_qk_at(q, k, cos, sin, self.rope_pos)
         cache.append_rows(k, v, self.append_pos)
+        if hasattr(cache, "table"):  # paged cache
+            return ops.attn_decode_paged(q[:, 0].contiguous(), cache.k, cache.v,
+                                         cache.table.table, self.attn_lens,
+                                         cache.k_scale, cache.v_scale,
+                                         max_len=self.max_len)
         return ops.attn_decode_varlen(q[:, 0].contiguous(), cache.k, cache.v,
                                       self.attn_lens, cache.k_scale, cache.v_scale,
                                       max_len=self.max_len)
@@ -316,10 +331,12 @@ def _sample_philox(logits, temperature, top_k, top_p, seed, i):
 
 def _generate_ragged(self, input_ids, max_new_tokens, temperature, top_k, seed,
                      kv_quant, prefill_chunk, prompt_lens, eos_token_id,
-                     pad_token_id, top_p=1.0, sampler="multinomial"):
+                     pad_token_id, top_p=1.0, sampler="multinomial",
+                     kv_layout="contiguous", kv_pages=None, kv_free_order=None):
     """Generation over a right-padded batch and/or with a stop token.
     Returns (tokens [B, s + max_new_tokens], lens [B])."""
     from .kv_cache import KVCache
+    from .paged_kv import PagedKVCache, PageTable, pages_for
 
     self.eval()
     b, s = input_ids.shape
@@ -334,9 +351,23 @@ def _generate_ragged(self, input_ids, max_new_tokens, temperature, top_k, seed,
     lens_out = n_cache.clone()
     if max_new_tokens <= 0:
         return tokens, lens_out
-    caches = [KVCache(b, total, self.cfg.n_kv_heads, self.cfg.head_dim, dev,
-                      dtype=self.embed.weight.dtype, quant=kv_quant)
-              for _ in self.blocks]
+    park = total  # where a finished sequence's append goes: nowhere
+    if kv_layout == "paged":
+        # every page of the call is reserved here, before the first step:
+        # sequence b gets the pages of its own L_b + max_new_tokens rows
+        rows = (n_cache + max_new_tokens).tolist()
+        need = sum(pages_for(r) for r in rows)
+        table = PageTable(b, pages_for(total), need if kv_pages is None else kv_pages,
+                          dev, free_order=kv_free_order)
+        table.reserve(rows)
+        caches = [PagedKVCache(table, self.cfg.n_kv_heads, self.cfg.head_dim, dev,
+                               dtype=self.embed.weight.dtype, quant=kv_quant)
+                  for _ in self.blocks]
+        park = table.max_rows
+    else:
+        caches = [KVCache(b, total, self.cfg.n_kv_heads, self.cfg.head_dim, dev,
+                          dtype=self.embed.weight.dtype, quant=kv_quant)
+                  for _ in self.blocks]
     gen = None
     if seed is not None:
         gen = torch.Generator(device=dev).manual_seed(seed)
@@ -362,7 +393,7 @@ def _generate_ragged(self, input_ids, max_new_tokens, temperature, top_k, seed,
                 break
         if i == max_new_tokens - 1:
             break
-        step = RaggedStep(n_cache, alive, total, self.rope_cos.shape[0],
+        step = RaggedStep(n_cache, alive, park, self.rope_cos.shape[0],
                           max_len=min(s + i + 1, total))
         x = self.embed(torch.where(alive[:, None], nxt, torch.full_like(nxt, pad_token_id)))
         for blk, cache in zip(self.blocks, caches):
@@ -377,7 +408,9 @@ def _generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
               seed: int | None = None, kv_quant: str | None = None,
               prefill_chunk: int | None = None, prompt_lens=None,
               eos_token_id: int | None = None, pad_token_id: int = 0,
-              top_p: float = 1.0, sampler: str = "multinomial"):
+              top_p: float = 1.0, sampler: str = "multinomial",
+              kv_layout: str = "contiguous", kv_pages: int | None = None,
+              kv_free_order=None):
     """Autoregressive generation with a per-layer KV cache (inference parity:
     the reference serves inference through the same executor surface).
     prefill_chunk feeds the prompt in pieces of at most that many tokens
@@ -396,16 +429,28 @@ def _generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
     the i-th new token of row b from u = ops.philox_uniform(seed, i, B)[b]
     through ops.sample_token, which also provides nucleus sampling (top_p):
     the output is a function of (model, prompt, seed, parameters) alone, the
-    same in the graphed decoder."""
+    same in the graphed decoder.
+
+    kv_layout="paged" keeps the cache in a pool of 64-row pages
+    (models/paged_kv.py) instead of one [B, s + max_new_tokens] slab per
+    layer: sequence b is charged ceil((L_b + max_new_tokens) / 64) pages,
+    reserved before the first step. kv_pages is the pool size (default:
+    exactly what the batch needs; too few raise PagePoolExhausted) and
+    kv_free_order the order pages are handed out in (default ascending). The
+    call always runs the per-sequence route (full lengths without
+    prompt_lens) and returns what the contiguous call would."""
     from .kv_cache import KVCache
 
     check_sampler(sampler, temperature, top_p, seed)
     if prefill_chunk is not None and prefill_chunk < 1:
         raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
-    if prompt_lens is not None or eos_token_id is not None:
+    if kv_layout not in ("contiguous", "paged"):
+        raise ValueError(f"kv_layout must be 'contiguous' or 'paged', got {kv_layout!r}")
+    if kv_layout == "paged" or prompt_lens is not None or eos_token_id is not None:
         tokens, lens = _generate_ragged(
             self, input_ids, max_new_tokens, temperature, top_k, seed, kv_quant,
-            prefill_chunk, prompt_lens, eos_token_id, pad_token_id, top_p, sampler)
+            prefill_chunk, prompt_lens, eos_token_id, pad_token_id, top_p, sampler,
+            kv_layout, kv_pages, kv_free_order)
         return (tokens, lens) if prompt_lens is not None else tokens
     self.eval()
     b, s = input_ids.shape

@@ -56,14 +56,17 @@ from .interface import (  # noqa: E402
     apply_rope_qk,
     apply_rope_qk_at,
     attn_decode,
+    attn_decode_paged,
     attn_decode_varlen,
     attn_prefill,
+    attn_prefill_paged,
     cross_entropy_loss,
     extract_delta,
     flash_attention,
     fused_adamw,
     fused_nesterov,
     gelu,
+    kv_append_paged,
     layernorm,
     linear_skinny,
     philox_uniform,
@@ -86,6 +89,9 @@ __all__ = [
     "attn_decode",
     "attn_decode_varlen",
     "attn_prefill",
+    "attn_decode_paged",
+    "attn_prefill_paged",
+    "kv_append_paged",
     "swiglu",
     "flash_attention",
     "cross_entropy_loss",

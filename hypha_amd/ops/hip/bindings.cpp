@@ -126,6 +126,22 @@ torch::Tensor attn_prefill(torch::Tensor q, torch::Tensor kcache, torch::Tensor 
 torch::Tensor attn_prefill_fp8(torch::Tensor q, torch::Tensor kcache,
                                torch::Tensor vcache, torch::Tensor kscale,
                                torch::Tensor vscale, long pos);
+// paged KV cache (decode.hip, prefill.hip): pools [n_pages, 64, Hkv, D] and a
+// device block table int32 [B, max_pages]
+torch::Tensor attn_decode_paged(torch::Tensor q, torch::Tensor kpool, torch::Tensor vpool,
+                                std::optional<torch::Tensor> kscale,
+                                std::optional<torch::Tensor> vscale,
+                                torch::Tensor block_table, torch::Tensor lens,
+                                long max_len);
+torch::Tensor attn_prefill_paged(torch::Tensor q, torch::Tensor kpool, torch::Tensor vpool,
+                                 std::optional<torch::Tensor> kscale,
+                                 std::optional<torch::Tensor> vscale,
+                                 torch::Tensor block_table, long pos,
+                                 std::optional<torch::Tensor> seq_lens);
+void kv_append_paged_(torch::Tensor k, torch::Tensor v, torch::Tensor kpool,
+                      torch::Tensor vpool, std::optional<torch::Tensor> kscale,
+                      std::optional<torch::Tensor> vscale, torch::Tensor block_table,
+                      torch::Tensor pos, std::optional<torch::Tensor> lens);
 // skinny_gemm.hip (decode GEMV, M <= 8)
 torch::Tensor skinny_gemm(torch::Tensor x, torch::Tensor w);
 // sample.hip (temperature / top-k / top-p sampling, Philox uniforms)
@@ -185,6 +201,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kv_append_rows_", &kv_append_rows_);
   m.def("attn_prefill_varlen", &attn_prefill_varlen);
   m.def("attn_prefill_varlen_fp8", &attn_prefill_varlen_fp8);
+  m.def("attn_decode_paged", &attn_decode_paged);
+  m.def("attn_prefill_paged", &attn_prefill_paged);
+  m.def("kv_append_paged_", &kv_append_paged_);
   m.def("skinny_gemm", &skinny_gemm);
   m.def("sample_token", &sample_token);
   m.def("philox_uniform", &philox_uniform);

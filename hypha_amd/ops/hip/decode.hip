@@ -36,13 +36,20 @@ __device__ __forceinline__ float e4m3_to_f32(unsigned char b) {
 // QUANT=false: bf16 cache rows; QUANT=true: OCP e4m3 rows + one fp32
 // scale per (b, t, hkv) row (kscale/vscale) — dequantized during the LDS
 // staging pass, so phases A/B are identical and cache reads halve.
-template <int HD, bool QUANT>
+// PAGED=true: the cache is a pool [n_pages, TILE, Hkv, D] and logical row j of
+// sequence b is row j % TILE of page block_table[b, j / TILE]. A split's
+// tiles start at multiples of TILE, so one staged tile is one page: the only
+// code that differs is the tile's first row, found through one workgroup-
+// uniform table load per tile (clamped: a page id from device memory must
+// never address outside the pool). T_alloc is then max_pages * TILE.
+template <int HD, bool QUANT, bool PAGED = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(
     const short* __restrict__ qg, const short* __restrict__ kg,
     const short* __restrict__ vg, const float* __restrict__ kscale,
     const float* __restrict__ vscale, float* __restrict__ partial_o,
     float* __restrict__ partial_ml, int B, int Hq, int Hkv, int T_alloc, int t_in,
-    const int* __restrict__ t_dev, int t_stride, int nsplits, float scale) {
+    const int* __restrict__ t_dev, int t_stride, int nsplits, float scale,
+    const int* __restrict__ block_table, int max_pages, int n_pages) {
   constexpr int PITCH = HD + 8;  // shorts; 16B-aligned, conflict-free b128
   __shared__ __attribute__((aligned(16))) short k_t[TILE * PITCH];
   __shared__ __attribute__((aligned(16))) short v_t[TILE * PITCH];
@@ -104,6 +111,12 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
 
   for (int r0 = s0; r0 < s1; r0 += TILE) {
     const int rows = min(TILE, s1 - r0);
+    // paged: pool row index of this tile's row 0 (r0 < t <= max_pages * TILE)
+    long long prow0 = 0;
+    if (PAGED) {
+      const int page = block_table[(long long)b * max_pages + r0 / TILE];
+      prow0 = (long long)min(max(page, 0), n_pages - 1) * TILE;
+    }
     // ---- cooperative K/V tile staging (8 rows x 512B per instruction;
     //      fp8 mode dequantizes per-row-scaled e4m3 bytes on the way) ----
     if (!QUANT) {
@@ -111,7 +124,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
       for (int c = tid; c < TILE * LPR; c += 256) {
         int rr = c / LPR, off = (c % LPR) * 8;  // off in shorts
         if (rr < rows) {
-          long long src = base + (long long)(r0 + rr) * row_stride + off;
+          long long src = PAGED ? (prow0 + rr) * row_stride + (long long)hkv * HD + off
+                                : base + (long long)(r0 + rr) * row_stride + off;
           *reinterpret_cast<s16x8*>(k_t + rr * PITCH + off) =
               *reinterpret_cast<const s16x8*>(kg + src);
           *reinterpret_cast<s16x8*>(v_t + rr * PITCH + off) =
@@ -125,7 +139,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
       for (int c = tid; c < TILE * LPR; c += 256) {
         int rr = c / LPR, off = (c % LPR) * 8;
         if (rr < rows) {
-          long long srow = ((long long)b * T_alloc + (r0 + rr)) * Hkv + hkv;
+          long long srow = PAGED ? (prow0 + rr) * Hkv + hkv
+                                 : ((long long)b * T_alloc + (r0 + rr)) * Hkv + hkv;
           long long src = srow * HD + off;
           float ks = kscale[srow];
           float vs = vscale[srow];
@@ -238,14 +253,43 @@ torch::Tensor attn_decode_impl(torch::Tensor q, torch::Tensor kcache,
                                const torch::Tensor* t_dev,
                                const torch::Tensor* kscale = nullptr,
                                const torch::Tensor* vscale = nullptr,
-                               int t_stride = 0, long max_len = -1) {
+                               int t_stride = 0, long max_len = -1,
+                               const torch::Tensor* block_table = nullptr) {
   TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16 && q.dim() == 3);
   TORCH_CHECK(kcache.dim() == 4 && kcache.is_contiguous() && vcache.is_contiguous());
   const bool quant = kcache.dtype() == torch::kFloat8_e4m3fn;
   TORCH_CHECK(!quant || (kscale && vscale), "fp8 cache needs row scales");
   const int B = q.size(0), Hq = q.size(1), HD = q.size(2);
-  const int T_alloc = kcache.size(1), Hkv = kcache.size(2);
-  TORCH_CHECK(kcache.size(0) == B && kcache.size(3) == HD);
+  const int Hkv = kcache.size(2);
+  // paged: kcache/vcache are the pools [n_pages, TILE, Hkv, D] and the
+  // logical cache of a sequence is max_pages * TILE rows
+  int max_pages = 0, n_pages = 0;
+  const int* bt_ptr = nullptr;
+  if (block_table) {
+    TORCH_CHECK(block_table->is_cuda() && block_table->dtype() == torch::kInt32 &&
+                    block_table->is_contiguous() && block_table->dim() == 2 &&
+                    block_table->size(0) == B && block_table->size(1) >= 1,
+                "decode: block_table must be contiguous int32 [B, max_pages]");
+    TORCH_CHECK(kcache.is_cuda() && vcache.is_cuda() && kcache.size(1) == TILE &&
+                    kcache.size(0) >= 1 && vcache.sizes() == kcache.sizes() &&
+                    vcache.dtype() == kcache.dtype(),
+                "decode: pools must be [n_pages, 64, Hkv, D] of one dtype");
+    TORCH_CHECK(block_table->size(1) <= (1L << 24) && kcache.size(0) <= (1L << 24),
+                "decode: pool or table too large");
+    TORCH_CHECK(t_dev && t_stride == 1, "decode: a paged cache needs per-sequence lengths");
+    if (quant)
+      for (const torch::Tensor* sc : {kscale, vscale})
+        TORCH_CHECK(sc->is_cuda() && sc->dtype() == torch::kFloat32 &&
+                        sc->is_contiguous() &&
+                        sc->numel() == kcache.size(0) * (long)TILE * Hkv,
+                    "decode: scales must be contiguous fp32 [n_pages, 64, Hkv]");
+    max_pages = block_table->size(1);
+    n_pages = kcache.size(0);
+    bt_ptr = block_table->data_ptr<int>();
+  }
+  const int T_alloc = block_table ? max_pages * TILE : (int)kcache.size(1);
+  if (block_table) t = T_alloc;
+  TORCH_CHECK((block_table || kcache.size(0) == B) && kcache.size(3) == HD);
   TORCH_CHECK(t >= 1 && t <= T_alloc, "decode: bad cache length");
   TORCH_CHECK(Hq % Hkv == 0 && (HD == 64 || HD == 128), "decode: unsupported shape");
   TORCH_CHECK(Hq / Hkv <= 8, "decode: GQA group > 8 not supported");
@@ -277,13 +321,20 @@ torch::Tensor attn_decode_impl(torch::Tensor q, torch::Tensor kcache,
 
 #define DECODE_DISPATCH(HDV, QV)                                                       \
   do {                                                                                 \
-    hipLaunchKernelGGL((attn_decode_kernel<HDV, QV>), dim3(nsplits, B* Hkv),           \
+    if (block_table)                                                                   \
+      DECODE_LAUNCH(HDV, QV, true);                                                    \
+    else                                                                               \
+      DECODE_LAUNCH(HDV, QV, false);                                                   \
+  } while (0)
+#define DECODE_LAUNCH(HDV, QV, PV)                                                     \
+  do {                                                                                 \
+    hipLaunchKernelGGL((attn_decode_kernel<HDV, QV, PV>), dim3(nsplits, B* Hkv),       \
                        dim3(256), 0, stream, (const short*)q.data_ptr(),               \
                        (const short*)kcache.data_ptr(),                                \
                        (const short*)vcache.data_ptr(), ksp, vsp,                      \
                        partial_o.data_ptr<float>(),                                    \
                        partial_ml.data_ptr<float>(), B, Hq, Hkv, T_alloc, (int)t,      \
-                       t_ptr, t_stride, nsplits, scale);                               \
+                       t_ptr, t_stride, nsplits, scale, bt_ptr, max_pages, n_pages);   \
     hipLaunchKernelGGL(attn_decode_reduce_kernel<HDV>, dim3(B* Hq), dim3(128), 0,      \
                        stream, partial_o.data_ptr<float>(),                            \
                        partial_ml.data_ptr<float>(), (short*)out.data_ptr(), B, Hq,    \
@@ -299,6 +350,7 @@ torch::Tensor attn_decode_impl(torch::Tensor q, torch::Tensor kcache,
   else
     DECODE_DISPATCH(64, true);
 #undef DECODE_DISPATCH
+#undef DECODE_LAUNCH
   return out;
 }
 
@@ -351,7 +403,56 @@ torch::Tensor attn_decode_varlen_fp8(torch::Tensor q, torch::Tensor kcache,
                           1, max_len > 0 ? max_len : -1);
 }
 
+// Paged cache: kpool/vpool [n_pages, 64, Hkv, D] (bf16, or fp8 with scales
+// [n_pages, 64, Hkv]); block_table int32 [B, max_pages] on the device maps
+// logical row j of sequence b to row j % 64 of page block_table[b, j / 64].
+// lens as in attn_decode_varlen, clamped to [0, max_pages * 64]; table slots
+// at or past ceil(lens[b] / 64) are never read. For the same logical cache
+// and the same max_len the output equals attn_decode_varlen's bit for bit.
+torch::Tensor attn_decode_paged(torch::Tensor q, torch::Tensor kpool, torch::Tensor vpool,
+                                std::optional<torch::Tensor> kscale,
+                                std::optional<torch::Tensor> vscale,
+                                torch::Tensor block_table, torch::Tensor lens,
+                                long max_len) {
+  TORCH_CHECK(lens.dim() == 1 && lens.size(0) == q.size(0), "decode: lens must be [B]");
+  TORCH_CHECK(kscale.has_value() == vscale.has_value(), "decode: give both scales or none");
+  return attn_decode_impl(q, kpool, vpool, 0, &lens, kscale ? &*kscale : nullptr,
+                          vscale ? &*vscale : nullptr, 1, max_len > 0 ? max_len : -1,
+                          &block_table);
+}
+
 namespace {
+
+// One row of HD bf16 values -> e4m3 bytes + one fp32 scale, by one wave
+// (lane l of 64): the bytes and the scale KVCache._quantize_rows writes for
+// this row on the GPU, bit for bit, so that a row appended here and one
+// appended through the PyTorch path are the same row: there the scale is amax
+// times the fp32 reciprocal of 448 (how a tensor is divided by a host scalar),
+// and each element is DIVIDED by the scale. (x * (1 / scale) rounds twice and
+// lands on another e4m3 byte in about 2% of bf16 rows.)
+template <int HD>
+__device__ __forceinline__ void quantize_row_e4m3(const short* __restrict__ src,
+                                                  unsigned char* __restrict__ dst8,
+                                                  float* __restrict__ dsts,
+                                                  long long row, int l) {
+  float vals[HD / 64];
+  float mx = 0.f;
+#pragma unroll
+  for (int i = 0; i < HD / 64; ++i) {
+    vals[i] = bf2f(src[l + 64 * i]);
+    mx = fmaxf(mx, fabsf(vals[i]));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+  const float scale = fmaxf(mx, 1e-8f) * (1.0f / 448.0f);
+  if (l == 0) dsts[row] = scale;
+#pragma unroll
+  for (int i = 0; i < HD / 64; ++i) {
+    float a = fminf(fmaxf(vals[i] / scale, -448.f), 448.f);
+    dst8[row * HD + l + 64 * i] =
+        (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(a, a, 0, false) & 0xff);
+  }
+}
 
 // Fused single-token fp8 KV append: one launch quantizes the new k AND v
 // rows (per-row amax -> scale -> e4m3) and writes bytes + scales at the
@@ -376,30 +477,64 @@ __global__ __launch_bounds__(64) void kv_append_fp8_kernel(
   const long long p = pos[b * pos_stride];
   if (p < 0 || p >= T_alloc) return;
   const long long row = ((long long)b * T_alloc + p) * Hkv + h;
+  quantize_row_e4m3<HD>(src, dst8, dsts, row, l);
+}
 
-  float vals[HD / 64];
-  float mx = 0.f;
-#pragma unroll
-  for (int i = 0; i < HD / 64; ++i) {
-    vals[i] = bf2f(src[l + 64 * i]);
-    mx = fmaxf(mx, fabsf(vals[i]));
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-  // The bytes and the scale KVCache._quantize_rows writes for this row on the
-  // GPU, bit for bit, so that a row appended here and one appended through
-  // the PyTorch path are the same row: there the scale is amax times the
-  // fp32 reciprocal of 448 (how a tensor is divided by a host scalar), and
-  // each element is DIVIDED by the scale. (x * (1 / scale) rounds twice and
-  // lands on another e4m3 byte in about 2% of bf16 rows.)
-  const float scale = fmaxf(mx, 1e-8f) * (1.0f / 448.0f);
-  if (l == 0) dsts[row] = scale;
-#pragma unroll
-  for (int i = 0; i < HD / 64; ++i) {
-    float a = fminf(fmaxf(vals[i] / scale, -448.f), 448.f);
-    dst8[row * HD + l + 64 * i] =
-        (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(a, a, 0, false) & 0xff);
-  }
+// Paged append: pool row of logical position p of sequence b, or -1 when the
+// row is not to be written: p outside [0, max_pages * TILE) (a parked
+// sequence), p at or past lens[b] (a pad row of a right-padded chunk), or a
+// page id outside [0, n_pages). A clamped write would land in another
+// sequence's page, so an out-of-range id writes nothing. Uniform over the
+// workgroup.
+__device__ __forceinline__ long long paged_dst_row(const int* __restrict__ block_table,
+                                                   const int* __restrict__ lens, int b,
+                                                   long long p, int max_pages,
+                                                   int n_pages) {
+  if (p < 0 || p >= (long long)max_pages * TILE) return -1;
+  if (lens && p >= (long long)lens[b]) return -1;
+  const int page = block_table[(long long)b * max_pages + (int)(p / TILE)];
+  if (page < 0 || page >= n_pages) return -1;
+  return (long long)page * TILE + (int)(p % TILE);
+}
+
+// k/v [B, s, Hkv, D] bf16 -> fp8 pool: one wave per (b, i, h) row; quantized
+// by the device code of kv_append_fp8_kernel. blockIdx.y: 0 = k, 1 = v.
+template <int HD>
+__global__ __launch_bounds__(64) void kv_append_paged_fp8_kernel(
+    const short* __restrict__ kin, const short* __restrict__ vin,
+    unsigned char* __restrict__ k8, unsigned char* __restrict__ v8,
+    float* __restrict__ kscale, float* __restrict__ vscale,
+    const int* __restrict__ block_table, const long long* __restrict__ pos,
+    int pos_stride, const int* __restrict__ lens, int s, int Hkv, int max_pages,
+    int n_pages) {
+  const long long rh = blockIdx.x;  // (b * s + i) * Hkv + h
+  const int h = (int)(rh % Hkv);
+  const long long bi = rh / Hkv;
+  const int b = (int)(bi / s), i = (int)(bi % s);
+  const long long prow = paged_dst_row(block_table, lens, b, pos[b * pos_stride] + i,
+                                       max_pages, n_pages);
+  if (prow < 0) return;
+  const int which = blockIdx.y;
+  quantize_row_e4m3<HD>((which ? vin : kin) + rh * HD, which ? v8 : k8,
+                        which ? vscale : kscale, prow * Hkv + h, threadIdx.x);
+}
+
+// k/v [B, s, Hkv, D] bf16 -> bf16 pool: row (b, i) (Hkv * HD contiguous
+// elements) is copied as 16-byte vectors. blockIdx.y: 0 = k, 1 = v.
+__global__ __launch_bounds__(256) void kv_append_paged_bf16_kernel(
+    const short* __restrict__ kin, const short* __restrict__ vin,
+    short* __restrict__ kc, short* __restrict__ vc, const int* __restrict__ block_table,
+    const long long* __restrict__ pos, int pos_stride, const int* __restrict__ lens,
+    int s, int row_elems, int max_pages, int n_pages) {
+  const long long bi = blockIdx.x;  // b * s + i
+  const int b = (int)(bi / s), i = (int)(bi % s);
+  const long long prow = paged_dst_row(block_table, lens, b, pos[b * pos_stride] + i,
+                                       max_pages, n_pages);
+  if (prow < 0) return;
+  const short* src = (blockIdx.y ? vin : kin) + bi * row_elems;
+  short* dst = (blockIdx.y ? vc : kc) + prow * row_elems;
+  for (int c = threadIdx.x * 8; c < row_elems; c += 256 * 8)
+    *reinterpret_cast<s16x8*>(dst + c) = *reinterpret_cast<const s16x8*>(src + c);
 }
 
 // bf16 cache: the row of sequence b (Hkv * HD contiguous elements in bshd)
@@ -493,4 +628,78 @@ void kv_append_rows_(torch::Tensor k, torch::Tensor v, torch::Tensor kcache,
                      (short*)kcache.data_ptr(), (short*)vcache.data_ptr(),
                      (const long long*)pos.data_ptr<int64_t>(), (int)(Hkv * HD),
                      (int)T_alloc);
+}
+
+// Paged append: row i of k/v [B, s, Hkv, D] bf16 goes to logical position
+// p = pos[b * pos_stride] + i of sequence b, i.e. row p % 64 of page
+// block_table[b, p / 64] of the pools [n_pages, 64, Hkv, D]. pos int64 on the
+// device, 1 entry (the whole batch at one position) or B entries; lens
+// (optional int32 [B]): rows with p >= lens[b] are not written. A position
+// outside [0, max_pages * 64) or a page id outside [0, n_pages) writes
+// nothing. bf16 pool: vector copy; fp8 pool: quantized as kv_append_fp8_ does.
+void kv_append_paged_(torch::Tensor k, torch::Tensor v, torch::Tensor kpool,
+                      torch::Tensor vpool, std::optional<torch::Tensor> kscale,
+                      std::optional<torch::Tensor> vscale, torch::Tensor block_table,
+                      torch::Tensor pos, std::optional<torch::Tensor> lens) {
+  TORCH_CHECK(k.is_cuda() && v.is_cuda() && k.dim() == 4 && k.dtype() == torch::kBFloat16 &&
+                  v.dtype() == torch::kBFloat16 && k.is_contiguous() && v.is_contiguous() &&
+                  v.sizes() == k.sizes(),
+              "append_paged: k/v must be contiguous bf16 [B, s, Hkv, D]");
+  const long B = k.size(0), s = k.size(1), Hkv = k.size(2), HD = k.size(3);
+  TORCH_CHECK(kpool.is_cuda() && vpool.is_cuda() && kpool.dim() == 4 &&
+                  kpool.is_contiguous() && vpool.is_contiguous() &&
+                  vpool.sizes() == kpool.sizes() && vpool.dtype() == kpool.dtype() &&
+                  kpool.size(0) >= 1 && kpool.size(1) == TILE && kpool.size(2) == Hkv &&
+                  kpool.size(3) == HD,
+              "append_paged: pools must be contiguous [n_pages, 64, Hkv, D] of one dtype");
+  const long n_pages = kpool.size(0);
+  TORCH_CHECK(block_table.is_cuda() && block_table.dtype() == torch::kInt32 &&
+                  block_table.is_contiguous() && block_table.dim() == 2 &&
+                  block_table.size(0) == B && block_table.size(1) >= 1,
+              "append_paged: block_table must be contiguous int32 [B, max_pages]");
+  const long max_pages = block_table.size(1);
+  TORCH_CHECK(pos.is_cuda() && pos.dtype() == torch::kInt64 && pos.is_contiguous() &&
+                  pos.dim() == 1 && (pos.size(0) == 1 || pos.size(0) == B),
+              "append_paged: pos must be int64 [1] or [B] on the GPU");
+  const int pos_stride = pos.size(0) == B && B > 1 ? 1 : 0;
+  const int* lens_p = nullptr;
+  if (lens.has_value()) {
+    TORCH_CHECK(lens->is_cuda() && lens->dtype() == torch::kInt32 && lens->is_contiguous() &&
+                    lens->dim() == 1 && lens->size(0) == B,
+                "append_paged: lens must be contiguous int32 [B] on the GPU");
+    lens_p = lens->data_ptr<int>();
+  }
+  TORCH_CHECK(s >= 1 && B >= 1 && B * s * Hkv < (1L << 31) && max_pages <= (1L << 24) &&
+                  n_pages <= (1L << 24) && HD % 8 == 0 && Hkv * HD < (1L << 31),
+              "append_paged: unsupported shape");
+  const int* bt = block_table.data_ptr<int>();
+  const long long* pp = (const long long*)pos.data_ptr<int64_t>();
+  hipStream_t stream = hypha_stream();
+  if (kpool.dtype() == torch::kFloat8_e4m3fn) {
+    TORCH_CHECK(kscale.has_value() && vscale.has_value(),
+                "append_paged: fp8 pool needs row scales");
+    for (const torch::Tensor* sc : {&*kscale, &*vscale})
+      TORCH_CHECK(sc->is_cuda() && sc->dtype() == torch::kFloat32 && sc->is_contiguous() &&
+                      sc->numel() == n_pages * TILE * Hkv,
+                  "append_paged: scales must be contiguous fp32 [n_pages, 64, Hkv]");
+    TORCH_CHECK(HD == 64 || HD == 128, "append_paged: fp8 head dim must be 64 or 128");
+#define APPEND_PAGED_FP8(HDV)                                                            \
+  hipLaunchKernelGGL(kv_append_paged_fp8_kernel<HDV>, dim3((unsigned)(B * s * Hkv), 2),  \
+                     dim3(64), 0, stream, (const short*)k.data_ptr(),                    \
+                     (const short*)v.data_ptr(), (unsigned char*)kpool.data_ptr(),       \
+                     (unsigned char*)vpool.data_ptr(), kscale->data_ptr<float>(),        \
+                     vscale->data_ptr<float>(), bt, pp, pos_stride, lens_p, (int)s,      \
+                     (int)Hkv, (int)max_pages, (int)n_pages)
+    if (HD == 128)
+      APPEND_PAGED_FP8(128);
+    else
+      APPEND_PAGED_FP8(64);
+#undef APPEND_PAGED_FP8
+    return;
+  }
+  TORCH_CHECK(kpool.dtype() == torch::kBFloat16, "append_paged: pool must be bf16 or fp8");
+  hipLaunchKernelGGL(kv_append_paged_bf16_kernel, dim3((unsigned)(B * s), 2), dim3(256), 0,
+                     stream, (const short*)k.data_ptr(), (const short*)v.data_ptr(),
+                     (short*)kpool.data_ptr(), (short*)vpool.data_ptr(), bt, pp, pos_stride,
+                     lens_p, (int)s, (int)(Hkv * HD), (int)max_pages, (int)n_pages);
 }

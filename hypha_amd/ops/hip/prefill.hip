@@ -24,6 +24,13 @@
 //    holds s_b = max(0, len_b - pos) live q rows. s_b and len_b replace s and
 //    t in every bound below; a workgroup with no live row returns at once,
 //    and the (pre-zeroed) output rows >= s_b are never written.
+//  * PAGED=true: the cache is a pool [n_pages, KVB, Hkv, D] and logical row j
+//    of sequence b is row j % KVB of page block_table[b, j / KVB]. kv tiles
+//    start at multiples of KVB, so one staged tile is one page: load_tile
+//    looks the tile's page up (one workgroup-uniform load, clamped to the
+//    pool) and nothing else changes. It is only called for kv0 < kv_end, so
+//    a table slot past the sequence's pages is never read. T_alloc is then
+//    max_pages * KVB.
 // No lse, no backward. Grid (ceil(s/128), B*Hq): a short chunk against a
 // long prefix runs few workgroups (no split-KV).
 
@@ -49,12 +56,13 @@ __device__ __forceinline__ s16x8 dequant8(uint2 raw, float sc) {
   return o;
 }
 
-template <int HD, bool QUANT>
+template <int HD, bool QUANT, bool PAGED = false>
 __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
     const short* __restrict__ qg, const void* __restrict__ kgv,
     const void* __restrict__ vgv, const float* __restrict__ kscale,
     const float* __restrict__ vscale, short* __restrict__ og, int Hq, int Hkv,
-    int s, int pos, int T_alloc, float scale, const int* __restrict__ seq_lens) {
+    int s, int pos, int T_alloc, float scale, const int* __restrict__ seq_lens,
+    const int* __restrict__ block_table, int max_pages, int n_pages) {
   constexpr int KC = HD / 16;        // 16-wide k chunks over head dim
   constexpr int DBLK = HD / 32;      // 32-row d blocks
   __shared__ __attribute__((aligned(16))) short k_lds[KVB * HD];
@@ -113,11 +121,18 @@ __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
   uint2 kraw[KCH], vraw[VCH];  // fp8 mode: raw bytes
   float ksc[KCH], vsc = 0.f;   // fp8 mode: row scales
   auto load_tile = [&](int kv0) {
+    // paged: pool row index of this tile's row 0 (kv0 < kv_end <= max_pages * KVB)
+    long long prow0 = 0;
+    if (PAGED) {
+      const int page = block_table[(long long)b * max_pages + kv0 / KVB];
+      prow0 = (long long)min(max(page, 0), n_pages - 1) * KVB;
+    }
 #pragma unroll
     for (int c = 0; c < KCH; ++c) {
       const int row = attn_k_row<HD>(c, tid), e0 = attn_k_e0<HD>(c, tid);
       const bool ok = kv0 + row < kv_end;
-      const long long srow = (kvrow0 + kv0 + row) * Hkv + hkv;
+      const long long srow =
+          PAGED ? (prow0 + row) * Hkv + hkv : (kvrow0 + kv0 + row) * Hkv + hkv;
       if (QUANT) {
         kraw[c] = make_uint2(0u, 0u);
         ksc[c] = 0.f;
@@ -137,7 +152,8 @@ __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
     {
       const int kvr = attn_v_row(tid);
       const bool ok = kv0 + kvr < kv_end;
-      const long long srow = (kvrow0 + kv0 + kvr) * Hkv + hkv;
+      const long long srow =
+          PAGED ? (prow0 + kvr) * Hkv + hkv : (kvrow0 + kv0 + kvr) * Hkv + hkv;
       if (QUANT) vsc = ok ? vscale[srow] : 0.f;
 #pragma unroll
       for (int i = 0; i < VCH; ++i) {
@@ -191,7 +207,8 @@ __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
 torch::Tensor attn_prefill_impl(torch::Tensor q, torch::Tensor kcache,
                                 torch::Tensor vcache, const torch::Tensor* kscale,
                                 const torch::Tensor* vscale, long pos,
-                                const torch::Tensor* seq_lens = nullptr) {
+                                const torch::Tensor* seq_lens = nullptr,
+                                const torch::Tensor* block_table = nullptr) {
   TORCH_CHECK(q.is_cuda() && kcache.is_cuda() && vcache.is_cuda(),
               "prefill: tensors must be on the GPU");
   TORCH_CHECK(q.dim() == 4 && q.dtype() == torch::kBFloat16 && q.is_contiguous(),
@@ -199,12 +216,30 @@ torch::Tensor attn_prefill_impl(torch::Tensor q, torch::Tensor kcache,
   TORCH_CHECK(kcache.dim() == 4 && kcache.is_contiguous() && vcache.is_contiguous() &&
                   vcache.sizes() == kcache.sizes() && vcache.dtype() == kcache.dtype(),
               "prefill: k/v caches must be contiguous [B, T_alloc, Hkv, D] of one dtype");
+  // paged: kcache/vcache are the pools [n_pages, KVB, Hkv, D]; a sequence's
+  // logical cache is max_pages * KVB rows
+  long max_pages = 0, n_pages = 0;
+  const int* bt_ptr = nullptr;
+  if (block_table) {
+    TORCH_CHECK(block_table->is_cuda() && block_table->dtype() == torch::kInt32 &&
+                    block_table->is_contiguous() && block_table->dim() == 2 &&
+                    block_table->size(0) == q.size(0) && block_table->size(1) >= 1 &&
+                    block_table->size(1) <= (1L << 24),
+                "prefill: block_table must be contiguous int32 [B, max_pages]");
+    TORCH_CHECK(kcache.size(1) == KVB && kcache.size(0) >= 1 && kcache.size(0) <= (1L << 24),
+                "prefill: pools must be [n_pages, 64, Hkv, D]");
+    max_pages = block_table->size(1);
+    n_pages = kcache.size(0);
+    bt_ptr = block_table->data_ptr<int>();
+  }
   const bool quant = kcache.dtype() == torch::kFloat8_e4m3fn;
   TORCH_CHECK(quant || kcache.dtype() == torch::kBFloat16,
               "prefill: cache must be bf16 or float8_e4m3fn");
   const long B = q.size(0), s = q.size(1), Hq = q.size(2), HD = q.size(3);
-  const long T_alloc = kcache.size(1), Hkv = kcache.size(2);
-  TORCH_CHECK(kcache.size(0) == B && kcache.size(3) == HD, "prefill: q/cache shape mismatch");
+  const long T_alloc = block_table ? max_pages * KVB : kcache.size(1);
+  const long Hkv = kcache.size(2);
+  TORCH_CHECK((block_table || kcache.size(0) == B) && kcache.size(3) == HD,
+              "prefill: q/cache shape mismatch");
   TORCH_CHECK(HD == 64 || HD == 128, "prefill: head dim must be 64 or 128");
   TORCH_CHECK(Hkv >= 1 && Hq % Hkv == 0, "prefill: Hq must be a multiple of Hkv");
   TORCH_CHECK(s >= 1 && pos >= 0 && pos + s <= T_alloc,
@@ -217,8 +252,8 @@ torch::Tensor attn_prefill_impl(torch::Tensor q, torch::Tensor kcache,
     TORCH_CHECK(kscale && vscale, "prefill: fp8 cache needs row scales");
     for (const torch::Tensor* sc : {kscale, vscale})
       TORCH_CHECK(sc->is_cuda() && sc->dtype() == torch::kFloat32 && sc->is_contiguous() &&
-                      sc->dim() == 3 && sc->size(0) == B && sc->size(1) == T_alloc &&
-                      sc->size(2) == Hkv,
+                      sc->dim() == 3 && sc->size(0) == kcache.size(0) &&
+                      sc->size(1) == kcache.size(1) && sc->size(2) == Hkv,
                   "prefill: scales must be contiguous fp32 [B, T_alloc, Hkv]");
     ksp = kscale->data_ptr<float>();
     vsp = vscale->data_ptr<float>();
@@ -240,11 +275,18 @@ torch::Tensor attn_prefill_impl(torch::Tensor q, torch::Tensor kcache,
   hipStream_t stream = hypha_stream();
 
 #define PREFILL_LAUNCH(HDV, QV)                                                       \
-  hipLaunchKernelGGL((attn_prefill_kernel<HDV, QV>), grid, dim3(256), 0, stream,      \
+  do {                                                                                \
+    if (block_table)                                                                  \
+      PREFILL_LAUNCH_P(HDV, QV, true);                                                \
+    else                                                                              \
+      PREFILL_LAUNCH_P(HDV, QV, false);                                               \
+  } while (0)
+#define PREFILL_LAUNCH_P(HDV, QV, PV)                                                 \
+  hipLaunchKernelGGL((attn_prefill_kernel<HDV, QV, PV>), grid, dim3(256), 0, stream,  \
                      (const short*)q.data_ptr(), (const void*)kcache.data_ptr(),      \
                      (const void*)vcache.data_ptr(), ksp, vsp, (short*)o.data_ptr(),  \
                      (int)Hq, (int)Hkv, (int)s, (int)pos, (int)T_alloc, scale,        \
-                     lens_p)
+                     lens_p, bt_ptr, (int)max_pages, (int)n_pages)
   if (HD == 128 && !quant)
     PREFILL_LAUNCH(128, false);
   else if (HD == 128)
@@ -254,6 +296,7 @@ torch::Tensor attn_prefill_impl(torch::Tensor q, torch::Tensor kcache,
   else
     PREFILL_LAUNCH(64, true);
 #undef PREFILL_LAUNCH
+#undef PREFILL_LAUNCH_P
   return o;
 }
 
@@ -288,4 +331,20 @@ torch::Tensor attn_prefill_varlen_fp8(torch::Tensor q, torch::Tensor kcache,
                                       torch::Tensor vscale, long pos,
                                       torch::Tensor seq_lens) {
   return attn_prefill_impl(q, kcache, vcache, &kscale, &vscale, pos, &seq_lens);
+}
+
+// Paged cache: kpool/vpool [n_pages, 64, Hkv, D] (bf16, or fp8 with scales
+// [n_pages, 64, Hkv]) and block_table int32 [B, max_pages] on the device;
+// needs pos + s <= max_pages * 64. Semantics and, for the same logical cache,
+// output bits of attn_prefill / attn_prefill_varlen.
+torch::Tensor attn_prefill_paged(torch::Tensor q, torch::Tensor kpool, torch::Tensor vpool,
+                                 std::optional<torch::Tensor> kscale,
+                                 std::optional<torch::Tensor> vscale,
+                                 torch::Tensor block_table, long pos,
+                                 std::optional<torch::Tensor> seq_lens) {
+  TORCH_CHECK(kscale.has_value() == vscale.has_value(),
+              "prefill: give both scales or none");
+  return attn_prefill_impl(q, kpool, vpool, kscale ? &*kscale : nullptr,
+                           vscale ? &*vscale : nullptr, pos,
+                           seq_lens ? &*seq_lens : nullptr, &block_table);
 }

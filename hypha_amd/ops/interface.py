@@ -17,6 +17,9 @@ The HIP extension ABI (hypha_amd._C):
   attn_prefill_varlen(q, kcache, vcache, pos, seq_lens_i32) -> o  # + _fp8
   kv_append_fp8_(k, v, k8, v8, kscale, vscale, pos_i64[1])
   kv_append_rows_(k, v, kcache, vcache, kscale?, vscale?, pos_i64[B])
+  attn_decode_paged(q, kpool, vpool, kscale?, vscale?, table_i32, lens_i32, max_len) -> o
+  attn_prefill_paged(q, kpool, vpool, kscale?, vscale?, table_i32, pos, seq_lens_i32?) -> o
+  kv_append_paged_(k, v, kpool, vpool, kscale?, vscale?, table_i32, pos_i64, lens_i32?)
   adamw_step_(master, param, grad, m, v, lr, b1, b2, eps, wd, step)
   adamw8_step_(master, param, grad, m8, v8, m_scale, v_scale, ...)  # 8-bit state
   nesterov_step_(master, delta_bf16, momentum, lr, mu)
@@ -429,6 +432,168 @@ def _attention_cached_varlen(q, k, v, pos: int, seq_lens) -> torch.Tensor:
     p = torch.softmax(scores.masked_fill(mask[:, None], float("-inf")), dim=-1)
     o = (p @ vh).masked_fill(q_dead[:, None, :, None], 0.0)
     return o.to(q.dtype).transpose(1, 2)
+
+
+# ---------------------------------------------------------------------------
+# Paged KV cache: a pool of 64-row pages and one block table per batch
+# ---------------------------------------------------------------------------
+
+PAGE = reference.PAGE
+
+
+def _check_paged(name, kpool, vpool, block_table, batch, kscale, vscale):
+    """Shared argument checks of the paged ops; returns (quant, max_rows)."""
+    if (kpool.dim() != 4 or kpool.shape[1] != PAGE or vpool.shape != kpool.shape
+            or vpool.dtype != kpool.dtype or kpool.shape[0] < 1):
+        raise ValueError(f"{name}: kpool/vpool must be [n_pages, {PAGE}, Hkv, D] "
+                         "of one dtype")
+    if (block_table.dtype != torch.int32 or block_table.dim() != 2
+            or block_table.shape[0] != batch or block_table.shape[1] < 1):
+        raise ValueError(f"{name}: block_table must be int32 [B, max_pages]")
+    quant = kpool.dtype == torch.float8_e4m3fn
+    if quant:
+        if kscale is None or vscale is None:
+            raise ValueError(f"{name}: an fp8 pool needs kscale and vscale")
+        if kscale.shape != kpool.shape[:3] or vscale.shape != kpool.shape[:3]:
+            raise ValueError(f"{name}: scales must be [n_pages, {PAGE}, Hkv]")
+    return quant, block_table.shape[1] * PAGE
+
+
+def attn_decode_paged(q, kpool, vpool, block_table, lens, kscale=None, vscale=None,
+                      max_len: int | None = None) -> torch.Tensor:
+    """attn_decode_varlen over a paged cache.
+
+    q [B, Hq, D] bf16; kpool/vpool [n_pages, 64, Hkv, D] bf16 OR fp8-e4m3 with
+    scales [n_pages, 64, Hkv]; block_table int32 [B, max_pages] on q's device:
+    logical row j of sequence b is row j % 64 of page block_table[b, j // 64].
+    lens int32 [B] as in attn_decode_varlen, clamped to [0, max_pages * 64];
+    table slots at or past ceil(lens[b] / 64) are never read, the ones read are
+    clamped to the pool, and lens[b] == 0 reads neither table nor pool. max_len
+    (default max_pages * 64) only sizes the split grid. Graph-capturable as is.
+    For the same logical cache and the same max_len the native kernel's output
+    equals attn_decode_varlen's bit for bit (the kernel body is shared;
+    ops/hip/decode.hip). Returns [B, Hq, D] in q's dtype.
+    """
+    if q.dim() != 3:
+        raise ValueError("attn_decode_paged: q must be [B, Hq, D]")
+    quant, max_rows = _check_paged("attn_decode_paged", kpool, vpool, block_table,
+                                   q.shape[0], kscale, vscale)
+    if lens.dtype != torch.int32 or lens.shape != (q.shape[0],):
+        raise ValueError("attn_decode_paged: lens must be int32 [B]")
+    if max_len is None:
+        max_len = max_rows
+    if not 1 <= max_len <= max_rows:
+        raise ValueError(f"attn_decode_paged: max_len={max_len} outside "
+                         f"[1, {max_rows}]")
+    if use_native(q) and q.shape[-1] in (64, 128) and q.shape[1] <= 8 * kpool.shape[2]:
+        return _c().attn_decode_paged(q, kpool, vpool, kscale if quant else None,
+                                      vscale if quant else None, block_table, lens,
+                                      max_len)
+    # reference path: the contiguous reference on the gathered pages
+    g = reference.gather_pages
+    return attn_decode_varlen(
+        q, g(kpool, block_table), g(vpool, block_table), lens,
+        g(kscale, block_table) if quant else None,
+        g(vscale, block_table) if quant else None, max_len=max_len)
+
+
+def attn_prefill_paged(q, kpool, vpool, block_table, pos: int, kscale=None,
+                       vscale=None, seq_lens=None) -> torch.Tensor:
+    """attn_prefill over a paged cache (pools and block_table as in
+    attn_decode_paged). q [B, s, Hq, D], row i at absolute position pos + i;
+    needs pos + s <= max_pages * 64; the chunk's own rows are already
+    appended. seq_lens as in attn_prefill. A tile's page is looked up only
+    when the tile holds a row below the sequence's bound, so slots past a
+    sequence's pages are never read. For the same logical cache the native
+    kernel's output equals attn_prefill's bit for bit (ops/hip/prefill.hip).
+    """
+    if q.dim() != 4:
+        raise ValueError("attn_prefill_paged: q must be [B, s, Hq, D]")
+    quant, max_rows = _check_paged("attn_prefill_paged", kpool, vpool, block_table,
+                                   q.shape[0], kscale, vscale)
+    s = q.shape[1]
+    if pos < 0 or s < 1 or pos + s > max_rows:
+        raise ValueError(f"attn_prefill_paged: pos={pos}, s={s} do not fit "
+                         f"{max_rows} rows of pages")
+    if seq_lens is not None and (seq_lens.dtype != torch.int32
+                                 or seq_lens.shape != (q.shape[0],)):
+        raise ValueError("attn_prefill_paged: seq_lens must be int32 [B]")
+    if (use_native(q) and q.shape[-1] in (64, 128)
+            and q.shape[2] % kpool.shape[2] == 0):
+        return _c().attn_prefill_paged(q.contiguous(), kpool, vpool,
+                                       kscale if quant else None,
+                                       vscale if quant else None, block_table, pos,
+                                       seq_lens)
+    g = reference.gather_pages
+    return attn_prefill(
+        q, g(kpool, block_table), g(vpool, block_table), pos,
+        g(kscale, block_table) if quant else None,
+        g(vscale, block_table) if quant else None, seq_lens=seq_lens)
+
+
+def quantize_rows_e4m3(x: torch.Tensor):
+    """x [..., D] -> (e4m3 [..., D], fp32 scale [...]): KVCache._quantize_rows'
+    arithmetic (scale = amax / 448, elements divided by the scale)."""
+    amax = x.float().abs().amax(-1).clamp(min=1e-8)
+    scale = amax / 448.0
+    q = (x.float() / scale.unsqueeze(-1)).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+    return q, scale
+
+
+def kv_append_paged(k, v, kpool, vpool, block_table, pos, kscale=None, vscale=None,
+                    lens=None) -> None:
+    """Append k/v [B, s, Hkv, D] (s >= 1) into a paged cache, in place.
+
+    Row i of sequence b goes to logical position p = pos[b] + i (pos: int64
+    [B] on k's device, or int64 [1] / a Python int for one position for the
+    whole batch), i.e. row p % 64 of page block_table[b, p // 64]. The row is
+    written iff 0 <= p < max_pages * 64, the page id lies in [0, n_pages), and
+    p < lens[b] when lens (int32 [B]) is given: a right-padded chunk then
+    writes no pad rows, and a parked sequence (position at or past
+    max_pages * 64) writes nothing. An fp8 pool stores the bytes and scales of
+    KVCache._quantize_rows, bit for bit. With pos on the device the call is
+    graph-capturable (ops/hip/decode.hip kv_append_paged_*_kernel).
+    """
+    if k.dim() != 4 or v.shape != k.shape or k.shape[1] < 1:
+        raise ValueError("kv_append_paged: k/v must be [B, s, Hkv, D], s >= 1")
+    b, s = k.shape[:2]
+    quant, max_rows = _check_paged("kv_append_paged", kpool, vpool, block_table, b,
+                                   kscale, vscale)
+    if kpool.shape[2:] != k.shape[2:]:
+        raise ValueError("kv_append_paged: k/v and the pools differ in [Hkv, D]")
+    if not isinstance(pos, torch.Tensor):
+        pos = torch.tensor([int(pos)], dtype=torch.long, device=k.device)
+    if pos.dtype != torch.long or pos.dim() != 1 or pos.shape[0] not in (1, b):
+        raise ValueError("kv_append_paged: pos must be int64 [1] or [B]")
+    if lens is not None and (lens.dtype != torch.int32 or lens.shape != (b,)):
+        raise ValueError("kv_append_paged: lens must be int32 [B]")
+    d = k.shape[-1]
+    if (use_native(k) and k.dtype == torch.bfloat16
+            and (d in (64, 128) if quant else
+                 (kpool.dtype == torch.bfloat16 and d % 8 == 0))):
+        _c().kv_append_paged_(k.contiguous(), v.contiguous(), kpool, vpool,
+                              kscale if quant else None, vscale if quant else None,
+                              block_table, pos, lens)
+        return
+    # reference path: the same row selection in PyTorch
+    n_pages = kpool.shape[0]
+    p = pos.expand(b)[:, None] + torch.arange(s, device=k.device)[None, :]  # [B, s]
+    ok = (p >= 0) & (p < max_rows)
+    if lens is not None:
+        ok &= p < lens.to(torch.long)[:, None]
+    page = block_table.to(torch.long).gather(
+        1, (p // PAGE).clamp(0, block_table.shape[1] - 1))
+    ok &= (page >= 0) & (page < n_pages)
+    rows = (page * PAGE + p % PAGE)[ok]  # flat pool rows of the written (b, i)
+    for x, pool, scale in ((k, kpool, kscale), (v, vpool, vscale)):
+        flat = pool.view(torch.uint8) if quant else pool
+        flat = flat.view(n_pages * PAGE, *pool.shape[2:])
+        if quant:
+            xq, sc = quantize_rows_e4m3(x[ok])
+            flat[rows] = xq.view(torch.uint8)
+            scale.view(n_pages * PAGE, -1)[rows] = sc
+        else:
+            flat[rows] = x[ok].to(pool.dtype)
 
 
 def linear_skinny(x2d: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:

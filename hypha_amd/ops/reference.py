@@ -111,6 +111,33 @@ def attention_cached(
     return (p @ vh.float()).to(q.dtype).transpose(1, 2)
 
 
+PAGE = 64  # rows per KV page (= the kv tile of decode.hip and attn_tile.h)
+
+
+def gather_pages(pool: torch.Tensor, block_table: torch.Tensor,
+                 n_rows: int | None = None) -> torch.Tensor:
+    """Contiguous copy of a paged cache: pool [n_pages, 64, ...] and
+    block_table int [B, max_pages] -> [B, n_rows, ...], where logical row j of
+    sequence b is row j % 64 of page block_table[b, j // 64]. n_rows defaults
+    to max_pages * 64. Page ids are clamped to the pool, as the kernels clamp
+    them: the rows of a slot no sequence owns hold whatever that page holds."""
+    if pool.dim() < 2 or pool.shape[1] != PAGE or block_table.dim() != 2:
+        raise ValueError("gather_pages: pool must be [n_pages, 64, ...] and "
+                         "block_table [B, max_pages]")
+    b, max_pages = block_table.shape
+    if n_rows is None:
+        n_rows = max_pages * PAGE
+    if not 0 <= n_rows <= max_pages * PAGE:
+        raise ValueError(f"gather_pages: n_rows={n_rows} outside "
+                         f"[0, {max_pages * PAGE}]")
+    idx = block_table.to(torch.long).clamp(0, pool.shape[0] - 1)
+    fp8 = pool.dtype == torch.float8_e4m3fn  # no fp8 indexing kernel: bytes
+    src = pool.view(torch.uint8) if fp8 else pool
+    out = src[idx].reshape(b, max_pages * PAGE, *pool.shape[2:])[:, :n_rows]
+    out = out.contiguous()
+    return out.view(torch.float8_e4m3fn) if fp8 else out
+
+
 # ---------------------------------------------------------------------------
 # SwiGLU MLP activation
 # ---------------------------------------------------------------------------

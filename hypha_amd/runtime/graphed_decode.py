@@ -29,6 +29,13 @@ a step draws u = ops.philox_uniform(seed, step, B), picks with
 ops.sample_token (ops/hip/sample.hip), records u in u_log[:, step] and
 advances the counter inside the graph. The tokens are those of
 model.generate(sampler="philox") with the same seed and parameters.
+
+kv_layout="paged" keeps the cache in a pool of 64-row pages
+(models/paged_kv.py). A paged decoder serves EVERY call through the two ragged
+graphs (a uniform call is a ragged one with full lengths): the block table is
+static device state, refilled on the host before a call's first step with the
+pages of the whole call, so nothing is allocated inside a graph and a captured
+graph stays valid across calls.
 """
 
 from __future__ import annotations
@@ -38,12 +45,17 @@ import torch
 from hypha_amd import ops
 from hypha_amd.models.kv_cache import KVCache
 from hypha_amd.models.llama import RaggedStep, check_prompt_lens, prefill_ragged
+from hypha_amd.models.paged_kv import PagedKVCache, PageTable, pages_for
 
 
 class GraphedDecoder:
     def __init__(self, model, batch: int, prompt_len: int, max_new: int,
-                 kv_quant: str | None = None):
+                 kv_quant: str | None = None, kv_layout: str = "contiguous",
+                 kv_pages: int | None = None, kv_free_order=None):
         from hypha_amd import _C
+
+        if kv_layout not in ("contiguous", "paged"):
+            raise ValueError(f"kv_layout must be 'contiguous' or 'paged', got {kv_layout!r}")
 
         self._C = _C
         self.model = model
@@ -54,10 +66,25 @@ class GraphedDecoder:
         self.max_new = max_new
         self.kv_quant = kv_quant
         t_alloc = prompt_len + max_new
-        self.caches = [KVCache(batch, t_alloc, cfg.n_kv_heads, cfg.head_dim,
-                               dev, dtype=next(model.parameters()).dtype,
-                               quant=kv_quant)
-                       for _ in model.blocks]
+        self.kv_layout = kv_layout
+        self.table = None
+        if kv_layout == "paged":
+            max_pages = pages_for(t_alloc)
+            self.table = PageTable(batch, max_pages,
+                                   batch * max_pages if kv_pages is None else kv_pages,
+                                   dev, free_order=kv_free_order)
+            self.caches = [PagedKVCache(self.table, cfg.n_kv_heads, cfg.head_dim,
+                                        dev, dtype=next(model.parameters()).dtype,
+                                        quant=kv_quant)
+                           for _ in model.blocks]
+        else:
+            self.caches = [KVCache(batch, t_alloc, cfg.n_kv_heads, cfg.head_dim,
+                                   dev, dtype=next(model.parameters()).dtype,
+                                   quant=kv_quant)
+                           for _ in model.blocks]
+        # where a finished sequence's append goes (nothing is written there),
+        # and the bound that sizes the decode kernel's split grid
+        self.park = self.table.max_rows if self.table is not None else t_alloc
         self.tok = torch.zeros(batch, 1, dtype=torch.long, device=dev)
         self.pos = torch.zeros(1, dtype=torch.long, device=dev)
         self.t32 = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -161,7 +188,8 @@ class GraphedDecoder:
         """One ragged decode step over static device state (graph-capturable):
         sequence b's current token sits at position n_cache[b]."""
         m = self.model
-        step = RaggedStep(self.n_cache, self.alive, self.t_alloc, m.rope_cos.shape[0])
+        step = RaggedStep(self.n_cache, self.alive, self.park, m.rope_cos.shape[0],
+                          max_len=self.t_alloc)
         x = m.embed(self.tok)
         for blk, cache in zip(m.blocks, self.caches):
             x = blk(x, m.rope_cos, m.rope_sin, cache=cache, ragged=step)
@@ -178,6 +206,9 @@ class GraphedDecoder:
         lens = check_prompt_lens([s] * b if prompt_lens is None else prompt_lens,
                                  b, s, self.dev)
         total = s + max_new_tokens
+        if self.table is not None and max_new_tokens > 0:
+            # the pages of the whole call, before any step runs
+            self.table.reserve((lens + max_new_tokens).tolist())
         self.tokens_r.fill_(pad_token_id)
         in_prompt = torch.arange(s, device=self.dev)[None, :] < lens[:, None]
         self.tokens_r[:, :s] = torch.where(in_prompt, input_ids, self.tokens_r[:, :s])
@@ -247,6 +278,11 @@ class GraphedDecoder:
             self.s_topk.fill_(min(int(top_k), 2 ** 31 - 1))
             self.s_topp.fill_(top_p)
             self.u_log.zero_()
+        if self.table is not None:
+            m.eval()
+            return self._generate_ragged(input_ids, max_new_tokens, prefill_chunk,
+                                         prompt_lens, eos_token_id, pad_token_id,
+                                         sample)
         if prompt_lens is not None or eos_token_id is not None:
             m.eval()
             for cache in self.caches:

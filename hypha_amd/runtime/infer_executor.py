@@ -14,7 +14,7 @@ Job config: {"model", "data": <fetch ref>, "results": <send ref>?,
              "top_k", "top_p"?, "sampler": "philox"?, "seed"?,
              "num_batches", "kv_cache": "fp8"?,
              "prefill_chunk": <int>?, "pad_token_id": <int>?,
-             "eos_token_id": <int>?}
+             "eos_token_id": <int>?, "kv_layout": "paged"?, "kv_pages": <int>?}
 
 Llama-family jobs on GPU decode through the hipGraph-captured step
 (runtime/graphed_decode.py) when they are greedy, or when they sample with
@@ -30,6 +30,13 @@ prompt's length is its row without the trailing run of that id (at least one
 token is kept), each sequence continues directly after its own prompt, and
 the completion file gains a "lens" tensor (final valid length per sequence)
 next to "tokens". "eos_token_id" stops a sequence at that token.
+
+"kv_layout": "paged" keeps the KV cache in a pool of 64-row pages
+(models/paged_kv.py): a sequence is charged the pages of its own length
+instead of the batch's longest. "kv_pages" sizes the pool (default: what the
+batch shape can need at most in the graphed decoder, exactly what each batch
+needs on the eager path); a batch that needs more fails with
+PagePoolExhausted. The completions are those of the contiguous layout.
 """
 
 from __future__ import annotations
@@ -111,6 +118,14 @@ def main() -> int:
         prefill_chunk = int(prefill_chunk)
         if prefill_chunk < 1:
             raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
+    kv_layout = cfg.get("kv_layout", "contiguous")
+    if kv_layout not in ("contiguous", "paged"):
+        raise ValueError(f"unknown kv_layout {kv_layout!r}")
+    layout_kw = {}
+    if kv_layout == "paged":
+        layout_kw["kv_layout"] = "paged"
+        if cfg.get("kv_pages") is not None:
+            layout_kw["kv_pages"] = int(cfg["kv_pages"])
     pad_id = cfg.get("pad_token_id")
     eos_id = cfg.get("eos_token_id")
     ragged_kw = {}
@@ -129,7 +144,7 @@ def main() -> int:
         from hypha_amd.runtime.graphed_decode import GraphedDecoder
 
         graphed = GraphedDecoder(model, batch_size, seq_len, max_new,
-                                 kv_quant=cfg.get("kv_cache"))
+                                 kv_quant=cfg.get("kv_cache"), **layout_kw)
 
     done_batches = 0
     out_idx = 0
@@ -151,11 +166,13 @@ def main() -> int:
                 elif philox:
                     out = model.generate(prompts, max_new_tokens=max_new,
                                          prefill_chunk=prefill_chunk,
-                                         sampler="philox", **kw, **sample_kw)
+                                         sampler="philox", **kw, **sample_kw,
+                                         **layout_kw)
                 else:
                     out = model.generate(prompts, max_new_tokens=max_new,
                                          temperature=temperature, top_k=top_k,
-                                         seed=0, prefill_chunk=prefill_chunk, **kw)
+                                         seed=0, prefill_chunk=prefill_chunk, **kw,
+                                         **layout_kw)
                 result = {}
                 if pad_id is not None:
                     out, lens = out

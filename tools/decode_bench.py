@@ -44,7 +44,13 @@ def main():
                         "from [LO, HI] (fixed seed, HI <= --prefill), generated "
                         "through the per-sequence-length path; LO == HI runs a "
                         "uniform batch through that path")
+    p.add_argument("--paged", action="store_true",
+                   help="paged KV cache (64-row pages, block table) in the "
+                        "graphed decoder; needs --graph --ragged LO:HI. Prints "
+                        "the KV bytes either layout allocates for the batch drawn")
     args = p.parse_args()
+    if args.paged and not (args.graph and args.ragged is not None):
+        raise SystemExit("--paged needs --graph --ragged LO:HI")
 
     from hypha_amd import models
 
@@ -62,11 +68,35 @@ def main():
                         device=dev)
 
     kvq = "fp8" if args.kv_fp8 else None
+    lens = None
+    if args.ragged is not None:
+        lo, hi = (int(x) for x in args.ragged.split(":"))
+        if not 1 <= lo <= hi <= args.prefill:
+            raise SystemExit(f"--ragged {args.ragged}: need 1 <= LO <= HI <= --prefill")
+        g = torch.Generator().manual_seed(0)
+        lens = torch.randint(lo, hi + 1, (args.batch,), generator=g)
+    kv_note = ""
     if args.graph:
         from hypha_amd.runtime.graphed_decode import GraphedDecoder
 
+        layout = {}
+        if args.paged:
+            from hypha_amd.models.paged_kv import PAGE, kv_bytes, pages_for
+
+            # a count from shapes: the pool holds exactly the pages the drawn
+            # batch needs; the contiguous slab charges every sequence
+            # --prefill + new rows
+            new = args.decode + args.warmup
+            n_pages = sum(pages_for(n + new) for n in lens.tolist())
+            layout = dict(kv_layout="paged", kv_pages=n_pages)
+            cfg = model.cfg
+            shape = (cfg.n_layers, cfg.n_kv_heads, cfg.head_dim, kvq)
+            paged_b = kv_bytes(n_pages * PAGE, *shape)
+            dense_b = kv_bytes(args.batch * (args.prefill + new), *shape)
+            kv_note = (f"  [KV bytes: paged {paged_b} ({n_pages} pages), contiguous "
+                       f"{dense_b}, ratio {paged_b / dense_b:.3f}]")
         dec = GraphedDecoder(model, args.batch, args.prefill,
-                             args.decode + args.warmup, kv_quant=kvq)
+                             args.decode + args.warmup, kv_quant=kvq, **layout)
         gen = dec.generate
     else:
         import functools
@@ -91,12 +121,8 @@ def main():
     if args.ragged is not None:
         import functools
 
-        lo, hi = (int(x) for x in args.ragged.split(":"))
-        if not 1 <= lo <= hi <= args.prefill:
-            raise SystemExit(f"--ragged {args.ragged}: need 1 <= LO <= HI <= --prefill")
-        g = torch.Generator().manual_seed(0)
-        lens = torch.randint(lo, hi + 1, (args.batch,), generator=g)
         gen = functools.partial(gen, prompt_lens=lens)
+        tag += " paged" if args.paged else ""
         tag += (f" ragged {lo}:{hi} (mean {lens.float().mean().item():.0f}, "
                f"max {int(lens.max())})")
 
@@ -119,7 +145,7 @@ def main():
         assert out_lens.tolist() == (lens + args.decode + args.warmup).tolist()
     print(f"{args.model} b{args.batch} prefill{args.prefill}{tag}: "
           f"{toks / dt:.0f} decode tok/s  ({dt / args.decode * 1e3:.2f} ms/step)"
-          f"  [prefill+{args.warmup}: {t_short:.2f}s]")
+          f"  [prefill+{args.warmup}: {t_short:.2f}s]{kv_note}")
     assert out.shape[1] == args.prefill + args.decode + args.warmup
 
 
