@@ -499,12 +499,35 @@ std::vector<torch::Tensor> attn_bwd_ex(torch::Tensor q, torch::Tensor k, torch::
                                        torch::Tensor o, torch::Tensor dout,
                                        torch::Tensor lse, bool causal,
                                        const std::string& layout) {
+  // every check runs before any launch: a mis-shaped tensor reaching a
+  // kernel is an out-of-bounds access
+  auto bf16_dense = [](const torch::Tensor& t) {
+    return t.is_cuda() && t.dim() == 4 && t.dtype() == torch::kBFloat16 &&
+           t.is_contiguous();
+  };
+  TORCH_CHECK(bf16_dense(q), "attn_bwd: q must be a contiguous 4-D bf16 tensor");
+  TORCH_CHECK(layout == "bhsd" || layout == "bshd",
+              "attn_bwd: layout must be bhsd or bshd");
   const bool bshd = layout == "bshd";
   const int B = q.size(0);
   const int Hq = bshd ? q.size(2) : q.size(1);
   const int S = bshd ? q.size(1) : q.size(2);
   const int HD = q.size(3);
+  TORCH_CHECK(bf16_dense(k) && k.size(0) == B && k.size(3) == HD &&
+                  (bshd ? k.size(1) : k.size(2)) == S,
+              "attn_bwd: k must be a contiguous bf16 tensor with q's batch, seq len "
+              "and head dim");
   const int Hkv = bshd ? k.size(2) : k.size(1);
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "attn_bwd: Hq must be a multiple of Hkv");
+  TORCH_CHECK(bf16_dense(v) && v.sizes() == k.sizes(),
+              "attn_bwd: v must be a contiguous bf16 tensor of k's shape");
+  TORCH_CHECK(bf16_dense(o) && o.sizes() == q.sizes(),
+              "attn_bwd: o must be a contiguous bf16 tensor of q's shape");
+  TORCH_CHECK(bf16_dense(dout) && dout.sizes() == q.sizes(),
+              "attn_bwd: dout must be a contiguous bf16 tensor of q's shape");
+  TORCH_CHECK(lse.is_cuda() && lse.dtype() == torch::kFloat32 && lse.is_contiguous() &&
+                  lse.numel() == (long long)B * Hq * S,
+              "attn_bwd: lse must be a contiguous fp32 tensor of B*Hq*S elements");
   TORCH_CHECK(HD == 64 || HD == 128);
   TORCH_CHECK(S % 128 == 0, "seq len must be a multiple of 128");
   auto dk = torch::empty_like(k);

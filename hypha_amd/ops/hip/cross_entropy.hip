@@ -116,12 +116,16 @@ __global__ void ce_bwd_kernel(short* __restrict__ logits, const long* __restrict
 std::vector<torch::Tensor> ce_fwd(torch::Tensor logits, torch::Tensor targets) {
   TORCH_CHECK(logits.dim() == 2 && logits.dtype() == torch::kBFloat16 &&
               logits.is_contiguous());
-  TORCH_CHECK(targets.dtype() == torch::kInt64);
+  TORCH_CHECK(logits.is_cuda() && targets.is_cuda() &&
+                  targets.dtype() == torch::kInt64 && targets.is_contiguous() &&
+                  targets.numel() == logits.size(0),
+              "ce_fwd: targets must be a contiguous int64 tensor of N elements");
   long long N = logits.size(0);
   int V = logits.size(1);
   auto lse = torch::empty({N}, logits.options().dtype(torch::kFloat32));
   auto loss = torch::zeros({}, logits.options().dtype(torch::kFloat32));
   auto nv = torch::zeros({}, logits.options().dtype(torch::kInt32));
+  if (N == 0) return {loss, lse, nv};  // a zero-sized grid is a launch error
   hipStream_t stream = hypha_stream();
   hipLaunchKernelGGL(ce_fwd_kernel, dim3((unsigned)N), dim3(256), 0, stream,
                      (const short*)logits.data_ptr(), targets.data_ptr<long>(),
@@ -132,8 +136,18 @@ std::vector<torch::Tensor> ce_fwd(torch::Tensor logits, torch::Tensor targets) {
 
 torch::Tensor ce_bwd_(torch::Tensor logits, torch::Tensor targets, torch::Tensor lse,
                       double scale) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 &&
+                  logits.dtype() == torch::kBFloat16 && logits.is_contiguous(),
+              "ce_bwd_: logits must be a contiguous 2-D bf16 tensor");
+  TORCH_CHECK(targets.is_cuda() && targets.dtype() == torch::kInt64 &&
+                  targets.is_contiguous() && targets.numel() == logits.size(0),
+              "ce_bwd_: targets must be a contiguous int64 tensor of N elements");
+  TORCH_CHECK(lse.is_cuda() && lse.dtype() == torch::kFloat32 && lse.is_contiguous() &&
+                  lse.numel() == logits.size(0),
+              "ce_bwd_: lse must be a contiguous fp32 tensor of N elements");
   long long N = logits.size(0);
   int V = logits.size(1);
+  if (N == 0) return logits;
   hipStream_t stream = hypha_stream();
   hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)N), dim3(256), 0, stream,
                      (short*)logits.data_ptr(), targets.data_ptr<long>(),

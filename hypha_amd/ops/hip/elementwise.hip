@@ -241,7 +241,11 @@ __global__ void swiglu_bwd_kernel(const short* __restrict__ dout,
 }
 
 torch::Tensor swiglu_fwd(torch::Tensor gate, torch::Tensor up) {
-  TORCH_CHECK(gate.dtype() == torch::kBFloat16 && gate.is_contiguous());
+  TORCH_CHECK(gate.is_cuda() && gate.dtype() == torch::kBFloat16 && gate.is_contiguous(),
+              "swiglu_fwd: gate must be a contiguous bf16 tensor");
+  TORCH_CHECK(up.is_cuda() && up.dtype() == torch::kBFloat16 && up.is_contiguous() &&
+                  up.sizes() == gate.sizes(),
+              "swiglu_fwd: up must be a contiguous bf16 tensor of gate's shape");
   auto out = torch::empty_like(gate);
   long long n = gate.numel();
   hipStream_t stream = hypha_stream();
@@ -253,6 +257,12 @@ torch::Tensor swiglu_fwd(torch::Tensor gate, torch::Tensor up) {
 
 std::vector<torch::Tensor> swiglu_bwd(torch::Tensor dout, torch::Tensor gate,
                                       torch::Tensor up) {
+  TORCH_CHECK(gate.is_cuda() && gate.dtype() == torch::kBFloat16 && gate.is_contiguous(),
+              "swiglu_bwd: gate must be a contiguous bf16 tensor");
+  for (const torch::Tensor* t : {&up, &dout})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kBFloat16 && t->is_contiguous() &&
+                    t->sizes() == gate.sizes(),
+                "swiglu_bwd: up and dout must be contiguous bf16 tensors of gate's shape");
   auto dgate = torch::empty_like(gate);
   auto dup = torch::empty_like(up);
   long long n = gate.numel();

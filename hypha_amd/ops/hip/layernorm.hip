@@ -186,18 +186,46 @@ __global__ void gelu_bwd_kernel(const short* __restrict__ dy, const short* __res
   }
 }
 
+// Host-side argument checks; they run before any launch (a mis-shaped tensor
+// reaching a kernel is an out-of-bounds access).
+void ln_check_x(const torch::Tensor& x) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.dtype() == torch::kBFloat16 &&
+                  x.is_contiguous(),
+              "x must be a contiguous 2-D bf16 tensor");
+  TORCH_CHECK(x.size(1) % 8 == 0, "D must be a multiple of 8");
+}
+
+void ln_check_like(const torch::Tensor& t, const torch::Tensor& x, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.dtype() == torch::kBFloat16 && t.is_contiguous() &&
+                  t.sizes() == x.sizes(),
+              what, " must be a contiguous bf16 tensor of x's shape");
+}
+
+void ln_check_vec(const torch::Tensor& w, long long D, const char* what) {
+  TORCH_CHECK(w.is_cuda() && w.dtype() == torch::kBFloat16 && w.is_contiguous() &&
+                  w.numel() == D,
+              what, " must be a contiguous bf16 tensor of D elements");
+}
+
+void ln_check_stat(const torch::Tensor& t, long long N, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.dtype() == torch::kFloat32 && t.is_contiguous() &&
+                  t.numel() == N,
+              what, " must be a contiguous fp32 tensor of N elements");
+}
+
 }  // namespace
 
 std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
                                          torch::Tensor b, double eps) {
-  TORCH_CHECK(x.dim() == 2 && x.dtype() == torch::kBFloat16 && x.is_contiguous());
-  TORCH_CHECK(x.size(1) % 8 == 0, "D must be a multiple of 8");
-  TORCH_CHECK(w.dtype() == torch::kBFloat16 && b.dtype() == torch::kBFloat16);
+  ln_check_x(x);
+  ln_check_vec(w, x.size(1), "w");
+  ln_check_vec(b, x.size(1), "b");
   long long N = x.size(0);
   int D = (int)x.size(1);
   auto y = torch::empty_like(x);
   auto mean = torch::empty({N}, x.options().dtype(torch::kFloat32));
   auto rstd = torch::empty({N}, x.options().dtype(torch::kFloat32));
+  if (N == 0) return {y, mean, rstd};  // a zero-sized grid is a launch error
   hipLaunchKernelGGL(layernorm_fwd_kernel, dim3((unsigned)N), dim3(256), 0,
                      hypha_stream(), (const short*)x.data_ptr(),
                      (const short*)w.data_ptr(), (const short*)b.data_ptr(),
@@ -209,11 +237,17 @@ std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
 std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
                                          torch::Tensor w, torch::Tensor mean,
                                          torch::Tensor rstd) {
+  ln_check_x(x);
+  ln_check_like(dy, x, "dy");
+  ln_check_vec(w, x.size(1), "w");
+  ln_check_stat(mean, x.size(0), "mean");
+  ln_check_stat(rstd, x.size(0), "rstd");
   long long N = x.size(0);
   int D = (int)x.size(1);
   auto dx = torch::empty_like(x);
   auto dw = torch::zeros({D}, x.options().dtype(torch::kFloat32));
   auto db = torch::zeros({D}, x.options().dtype(torch::kFloat32));
+  if (N == 0) return {dx, dw, db};
   hipStream_t stream = hypha_stream();
   hipLaunchKernelGGL(layernorm_bwd_dx_kernel, dim3((unsigned)N), dim3(256), 0, stream,
                      (const short*)dy.data_ptr(), (const short*)x.data_ptr(),
@@ -233,7 +267,7 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
 }
 
 torch::Tensor gelu_fwd(torch::Tensor x) {
-  TORCH_CHECK(x.dtype() == torch::kBFloat16 && x.is_contiguous());
+  TORCH_CHECK(x.is_cuda() && x.dtype() == torch::kBFloat16 && x.is_contiguous());
   long long n = x.numel();
   auto y = torch::empty_like(x);
   hipLaunchKernelGGL(gelu_fwd_kernel, dim3(elementwise_grid((n + 7) / 8)), dim3(256), 0,
@@ -242,6 +276,11 @@ torch::Tensor gelu_fwd(torch::Tensor x) {
 }
 
 torch::Tensor gelu_bwd(torch::Tensor dy, torch::Tensor x) {
+  TORCH_CHECK(x.is_cuda() && x.dtype() == torch::kBFloat16 && x.is_contiguous(),
+              "gelu_bwd: x must be a contiguous bf16 tensor");
+  TORCH_CHECK(dy.is_cuda() && dy.dtype() == torch::kBFloat16 && dy.is_contiguous() &&
+                  dy.sizes() == x.sizes(),
+              "gelu_bwd: dy must be a contiguous bf16 tensor of x's shape");
   long long n = x.numel();
   auto dx = torch::empty_like(x);
   hipLaunchKernelGGL(gelu_bwd_kernel, dim3(elementwise_grid((n + 7) / 8)), dim3(256), 0,

@@ -18,6 +18,35 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* scratch) {
   return total;
 }
 
+// Host-side argument checks shared by the row kernels' entry points. They run
+// before any launch: a mis-shaped tensor reaching a kernel is an
+// out-of-bounds access.
+static void check_rows_bf16(const torch::Tensor& t, const torch::Tensor& x,
+                            const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.dtype() == torch::kBFloat16 && t.is_contiguous() &&
+                  t.sizes() == x.sizes(),
+              what, " must be a contiguous bf16 tensor of x's shape");
+}
+
+static void check_weight_bf16(const torch::Tensor& w, long long D, const char* what) {
+  TORCH_CHECK(w.is_cuda() && w.dtype() == torch::kBFloat16 && w.is_contiguous() &&
+                  w.numel() == D,
+              what, " must be a contiguous bf16 tensor of D elements");
+}
+
+static void check_row_stat(const torch::Tensor& t, long long N, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.dtype() == torch::kFloat32 && t.is_contiguous() &&
+                  t.numel() == N,
+              what, " must be a contiguous fp32 tensor of N elements");
+}
+
+static void check_x_rows(const torch::Tensor& x) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.dtype() == torch::kBFloat16 &&
+                  x.is_contiguous(),
+              "x must be a contiguous 2-D bf16 tensor");
+  TORCH_CHECK(x.size(1) % 8 == 0, "D must be a multiple of 8");
+}
+
 __global__ void rmsnorm_fwd_kernel(const short* __restrict__ x, const short* __restrict__ w,
                                    short* __restrict__ y, float* __restrict__ rstd_out,
                                    int D, float eps) {
@@ -107,12 +136,13 @@ __global__ void rmsnorm_bwd_dw_kernel(const short* __restrict__ dy,
 }
 
 std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w, double eps) {
-  TORCH_CHECK(x.dim() == 2 && x.dtype() == torch::kBFloat16 && x.is_contiguous());
-  TORCH_CHECK(x.size(1) % 8 == 0, "D must be a multiple of 8");
+  check_x_rows(x);
+  check_weight_bf16(w, x.size(1), "w");
   long long N = x.size(0);
   int D = x.size(1);
   auto y = torch::empty_like(x);
   auto rstd = torch::empty({N}, x.options().dtype(torch::kFloat32));
+  if (N == 0) return {y, rstd};  // a zero-sized grid is a launch error
   hipStream_t stream = hypha_stream();
   hipLaunchKernelGGL(rmsnorm_fwd_kernel, dim3((unsigned)N), dim3(256), 0, stream,
                      (const short*)x.data_ptr(), (const short*)w.data_ptr(),
@@ -122,10 +152,15 @@ std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w, double 
 
 std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x, torch::Tensor w,
                                        torch::Tensor rstd) {
+  check_x_rows(x);
+  check_rows_bf16(dy, x, "dy");
+  check_weight_bf16(w, x.size(1), "w");
+  check_row_stat(rstd, x.size(0), "rstd");
   long long N = x.size(0);
   int D = x.size(1);
   auto dx = torch::empty_like(x);
   auto dw = torch::zeros({D}, x.options().dtype(torch::kFloat32));
+  if (N == 0) return {dx, dw};
   hipStream_t stream = hypha_stream();
   hipLaunchKernelGGL(rmsnorm_bwd_dx_kernel, dim3((unsigned)N), dim3(256), 0, stream,
                      (const short*)dy.data_ptr(), (const short*)x.data_ptr(),
@@ -237,14 +272,16 @@ __global__ void add_rmsnorm_bwd_dx_kernel(const short* __restrict__ dy,
 
 std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor a, torch::Tensor b,
                                            torch::Tensor w, double eps) {
-  TORCH_CHECK(a.dim() == 2 && a.dtype() == torch::kBFloat16 && a.is_contiguous());
-  TORCH_CHECK(b.sizes() == a.sizes() && b.is_contiguous());
-  TORCH_CHECK(a.size(1) % 8 == 0 && a.size(1) <= 16384);
+  check_x_rows(a);
+  check_rows_bf16(b, a, "b");
+  TORCH_CHECK(a.size(1) <= 16384, "add_rmsnorm: D must be at most 16384");
+  check_weight_bf16(w, a.size(1), "w");
   long long N = a.size(0);
   int D = a.size(1);
   auto h = torch::empty_like(a);
   auto y = torch::empty_like(a);
   auto rstd = torch::empty({N}, a.options().dtype(torch::kFloat32));
+  if (N == 0) return {h, y, rstd};
   hipStream_t stream = hypha_stream();
   hipLaunchKernelGGL(add_rmsnorm_fwd_kernel, dim3((unsigned)N), dim3(256), 0, stream,
                      (const short*)a.data_ptr(), (const short*)b.data_ptr(),
@@ -256,10 +293,16 @@ std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor a, torch::Tensor b,
 std::vector<torch::Tensor> add_rmsnorm_bwd(torch::Tensor dy, torch::Tensor dh,
                                            torch::Tensor h, torch::Tensor w,
                                            torch::Tensor rstd) {
+  check_x_rows(h);
+  check_rows_bf16(dy, h, "dy");
+  check_rows_bf16(dh, h, "dh");
+  check_weight_bf16(w, h.size(1), "w");
+  check_row_stat(rstd, h.size(0), "rstd");
   long long N = h.size(0);
   int D = h.size(1);
   auto dx = torch::empty_like(h);
   auto dw = torch::zeros({D}, h.options().dtype(torch::kFloat32));
+  if (N == 0) return {dx, dw};
   hipStream_t stream = hypha_stream();
   hipLaunchKernelGGL(add_rmsnorm_bwd_dx_kernel, dim3((unsigned)N), dim3(256), 0, stream,
                      (const short*)dy.data_ptr(), (const short*)dh.data_ptr(),

@@ -46,13 +46,24 @@ __global__ void rope_kernel(const short* __restrict__ x, short* __restrict__ out
 std::vector<torch::Tensor> rope_fwd_ex(torch::Tensor q, torch::Tensor k,
                                        torch::Tensor cos_t, torch::Tensor sin_t,
                                        bool inverse, const std::string& layout) {
-  TORCH_CHECK(q.dim() == 4 && q.dtype() == torch::kBFloat16 && q.is_contiguous());
+  TORCH_CHECK(q.is_cuda() && q.dim() == 4 && q.dtype() == torch::kBFloat16 &&
+              q.is_contiguous());
   TORCH_CHECK(cos_t.dtype() == torch::kFloat32 && cos_t.is_contiguous());
+  TORCH_CHECK(layout == "bhsd" || layout == "bshd", "rope: layout must be bhsd or bshd");
   const bool bshd = layout == "bshd";
   int D = q.size(3);
   int S = bshd ? q.size(1) : q.size(2);
   TORCH_CHECK(D % 8 == 0);
-  TORCH_CHECK(cos_t.size(0) >= S && cos_t.size(1) == D / 2, "rope table too small");
+  TORCH_CHECK(cos_t.is_cuda() && cos_t.dim() == 2 && cos_t.size(0) >= S &&
+                  cos_t.size(1) == D / 2,
+              "rope table too small");
+  TORCH_CHECK(sin_t.is_cuda() && sin_t.dtype() == torch::kFloat32 &&
+                  sin_t.is_contiguous() && sin_t.sizes() == cos_t.sizes(),
+              "rope: sin must be a contiguous fp32 table of cos's shape");
+  TORCH_CHECK(k.is_cuda() && k.dim() == 4 && k.dtype() == torch::kBFloat16 &&
+                  k.is_contiguous() && k.size(3) == D &&
+                  (bshd ? k.size(1) : k.size(2)) == S,
+              "rope: k must be a contiguous 4-D bf16 tensor with q's seq len and head dim");
   auto qo = torch::empty_like(q);
   auto ko = torch::empty_like(k);
   float sign = inverse ? -1.f : 1.f;

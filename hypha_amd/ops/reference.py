@@ -324,3 +324,104 @@ def sample_token(logits: torch.Tensor, u: torch.Tensor, temperature, top_k=0,
     last_mass = torch.where(keep & (m > 0), rank, 0).amax(-1, keepdim=True)
     j = torch.where(first_hit < v, first_hit, last_mass)
     return idx.gather(1, j)
+
+
+# ---------------------------------------------------------------------------
+# Stochastic rounding (ops/hip/lean_opt.hip, fp8_lean.hip): the per-element
+# hash and the fp32 -> bf16 dither, in int64 arithmetic masked to 32 bits (the
+# style of philox4x32), so a test can compare the kernels' rounding decisions
+# bit for bit.
+# ---------------------------------------------------------------------------
+
+def rnd_hash(idx: torch.Tensor, seed: int) -> torch.Tensor:
+    """The kernels' rnd_hash: idx int64 flat element indices (>= 0), seed taken
+    mod 2**32 -> int64 holding the 32-bit hash."""
+    idx = idx.to(torch.long)
+    x = (idx ^ (idx >> 31)) & _M32
+    x = (_mulhilo32(x, 0x9E3779B9)[1] + (int(seed) & _M32)) & _M32
+    x = x ^ (x >> 16)
+    x = _mulhilo32(x, 0x85EBCA6B)[1]
+    return x ^ (x >> 13)
+
+
+def f2bf_sr(f: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+    """The kernels' f2bf_sr: add the low 16 bits of r below the bf16 mantissa of
+    the fp32 f and truncate (NaN -> 0x7fc0). Returns bf16."""
+    bits = f.contiguous().view(torch.int32).to(torch.long) & _M32
+    out = ((bits + (r & 0xFFFF)) >> 16) & 0xFFFF
+    out = torch.where((bits & 0x7FFFFFFF) > 0x7F800000,
+                      torch.full_like(out, 0x7FC0), out)
+    return ((out ^ 0x8000) - 0x8000).to(torch.int16).view(torch.bfloat16)
+
+
+@torch.no_grad()
+def nesterov_bf16_step(theta: torch.Tensor, delta: torch.Tensor, mom: torch.Tensor,
+                       lr: float, mu: float, seed: int):
+    """bf16 outer Nesterov chunk (nesterov_bf16_): m = mu*mom + d and
+    t = theta + lr*(mu*m + d) in fp32; the kernel stores bf16(m) round-to-nearest
+    and theta = f2bf_sr(t, rnd_hash(i, seed)). Returns (t fp32, m fp32, the
+    stochastically rounded theta bf16); inputs are not modified."""
+    d = delta.float()
+    m = mu * mom.float() + d
+    t = theta.float() + lr * (mu * m + d)
+    idx = torch.arange(t.numel(), device=t.device).view(t.shape)
+    return t, m, f2bf_sr(t, rnd_hash(idx, seed))
+
+
+# ---------------------------------------------------------------------------
+# Block-quantised AdamW (ops/hip/adamw8.hip and the lean variants): m as uint8
+# codes around 127, sqrt(v) as uint8 codes, one fp32 absmax scale per block.
+# ---------------------------------------------------------------------------
+
+QBLOCK = 2048  # elements per quantisation block
+
+
+def _per_elem(scale: torch.Tensor, n: int) -> torch.Tensor:
+    return scale.repeat_interleave(QBLOCK)[:n]
+
+
+def block_absmax(x: torch.Tensor) -> torch.Tensor:
+    """max |x| over each QBLOCK of the flat x (the last block may be partial)."""
+    n = x.numel()
+    nb = (n + QBLOCK - 1) // QBLOCK
+    pad = torch.zeros(nb * QBLOCK, dtype=x.dtype, device=x.device)
+    pad[:n] = x.abs()
+    return pad.view(nb, QBLOCK).amax(dim=1)
+
+
+@torch.no_grad()
+def adamw8_step(master: torch.Tensor, grad: torch.Tensor, m8: torch.Tensor,
+                v8: torch.Tensor, m_scale: torch.Tensor, v_scale: torch.Tensor, *,
+                lr: float, beta1: float = 0.9, beta2: float = 0.95,
+                eps: float = 1e-8, weight_decay: float = 0.1, step: int):
+    """One step of the block-quantised AdamW kernels, in their order of fp32
+    operations: dequantise m = (m8 - 127) * ms and v = (v8 * vs)**2, update,
+    take each block's absmax, set the new scales am/127 and av/255 (1e-12 when
+    the block is all zero) and the new codes with rint and the kernels' clamps.
+
+    master is the fp32 weight going in (the fp32 master, or the dequantised
+    bf16/fp8 weight of the lean kernels). Nothing is modified. Returns
+    (w, m, sqrt_v, m8_new, v8_new, m_scale_new, v_scale_new); w, m and sqrt_v
+    are the fp32 values before any rounding."""
+    n = master.numel()
+    f32 = dict(dtype=torch.float32, device=master.device)
+    one = torch.tensor(1.0, **f32)
+    b1, b2 = torch.tensor(beta1, **f32), torch.tensor(beta2, **f32)
+    lr32, wd32 = torch.tensor(lr, **f32), torch.tensor(weight_decay, **f32)
+    inv_bc1 = one / (one - b1.pow(step))
+    inv_bc2 = one / (one - b2.pow(step))
+    g = grad.float()
+    m = (m8.float() - 127.0) * _per_elem(m_scale, n)
+    sv = v8.float() * _per_elem(v_scale, n)
+    v = sv * sv
+    m = b1 * m + (one - b1) * g
+    v = b2 * v + (one - b2) * g * g
+    denom = (v * inv_bc2).sqrt() + torch.tensor(eps, **f32)
+    w = master.float() * (one - lr32 * wd32) - lr32 * inv_bc1 * m / denom
+    sqrt_v = v.sqrt()
+    am, av = block_absmax(m), block_absmax(sqrt_v)
+    ms_new = torch.where(am > 0, am / 127.0, torch.full_like(am, 1e-12))
+    vs_new = torch.where(av > 0, av / 255.0, torch.full_like(av, 1e-12))
+    qm = (torch.round(m / _per_elem(ms_new, n)) + 127.0).clamp(0, 254)
+    qv = torch.round(sqrt_v / _per_elem(vs_new, n)).clamp(0, 255)
+    return w, m, sqrt_v, qm.to(torch.uint8), qv.to(torch.uint8), ms_new, vs_new
