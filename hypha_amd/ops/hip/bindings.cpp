@@ -64,6 +64,10 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k, torch::Ten
                                     bool causal);
 std::vector<torch::Tensor> attn_fwd_ex(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                                        bool causal, const std::string& layout);
+void attn_bwd_into(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o,
+                   torch::Tensor dout, torch::Tensor lse, bool causal,
+                   const std::string& layout, torch::Tensor dq, torch::Tensor dk,
+                   torch::Tensor dv);
 std::vector<torch::Tensor> attn_bwd_ex(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                                        torch::Tensor o, torch::Tensor dout,
                                        torch::Tensor lse, bool causal,
@@ -71,6 +75,7 @@ std::vector<torch::Tensor> attn_bwd_ex(torch::Tensor q, torch::Tensor k, torch::
 // probe.hip (MFMA fragment-layout verification)
 torch::Tensor mfma_probe_32x32x16(torch::Tensor a, torch::Tensor b);
 torch::Tensor mfma_probe_16x16x32(torch::Tensor a, torch::Tensor b);
+torch::Tensor mfma_probe_acc_operand(torch::Tensor a, torch::Tensor m1, torch::Tensor m2);
 // fp8_cast.hip
 std::vector<torch::Tensor> fp8_cast_transpose(torch::Tensor x, torch::Tensor scale,
                                               torch::Tensor partials, long skip_t);
@@ -177,8 +182,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd", &attn_bwd);
   m.def("attn_fwd_ex", &attn_fwd_ex);
   m.def("attn_bwd_ex", &attn_bwd_ex);
+  m.def("attn_bwd_into", &attn_bwd_into);
   m.def("mfma_probe_32x32x16", &mfma_probe_32x32x16);
   m.def("mfma_probe_16x16x32", &mfma_probe_16x16x32);
+  m.def("mfma_probe_acc_operand", &mfma_probe_acc_operand);
   m.def("fp8_cast_transpose", &fp8_cast_transpose, pybind11::arg("x"),
         pybind11::arg("scale"), pybind11::arg("partials"),
         pybind11::arg("skip_t") = 0);
