@@ -39,7 +39,7 @@ for _name in llama.PRESETS:
         continue  # the true GPT-2 arch wins that name
     register(_name, (lambda n: (lambda **o: llama.build_model(n, **o)))(_name))
 for _name in gpt2.PRESETS:
-    register(_name, (lambda n: (lambda **o: gpt2.build_model(n))) (_name))
+    register(_name, (lambda n: (lambda **o: gpt2.build_model(n, **o)))(_name))
 for _name in moe.PRESETS:
     register(_name, (lambda n: (lambda **o: moe.build_model(n, **o)))(_name))
 

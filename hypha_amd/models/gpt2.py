@@ -184,5 +184,10 @@ class GPT2ForCausalLM(nn.Module):
         return tokens
 
 
-def build_model(name: str) -> GPT2ForCausalLM:
-    return GPT2ForCausalLM(PRESETS[name])
+def build_model(name: str, **overrides) -> GPT2ForCausalLM:
+    cfg = PRESETS[name]
+    if overrides:
+        from dataclasses import replace
+
+        cfg = replace(cfg, **overrides)
+    return GPT2ForCausalLM(cfg)

@@ -46,6 +46,19 @@ def test_registry_lists_flagships():
         assert name in av
 
 
+def test_gpt2_registry_takes_overrides():
+    import pytest
+
+    m = models.build("gpt2-tiny", hidden_size=128, n_heads=2, n_positions=256)
+    assert (m.cfg.hidden_size, m.cfg.n_heads, m.cfg.n_positions) == (128, 2, 256)
+    assert m.wpe.weight.shape == (256, 128)
+    assert m.blocks[0].attn_qkv.weight.shape == (384, 128)
+    assert m.cfg.n_layers == 2  # what is not overridden stays the preset's
+    assert models.build("gpt2-tiny").cfg.hidden_size == 64  # the preset is untouched
+    with pytest.raises(TypeError):
+        models.build("gpt2-tiny", no_such_field=1)
+
+
 def test_moe_tiny_forward_backward():
     torch.manual_seed(0)
     m = models.build("moe-tiny")
