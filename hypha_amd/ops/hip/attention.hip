@@ -1,13 +1,7 @@
-// Fused causal GQA flash attention, forward + backward, for CDNA4 (gfx950).
+// Fused causal GQA flash attention, backward, for CDNA4 (gfx950); the
+// forward is attn_fwd.hip's.
 // Covers K1's attention piece natively — the reference
 // delegates this to HF/PyTorch SDPA inside its Python executor.
-//
-// Forward (one workgroup = 4 waves = 128 q rows; KV tile = 64): the tile
-// pipeline — LDS images, swapped QK^T, lane-local online softmax, in-register
-// P pack, transposed O and its epilogue — is attn_tile.h's, shared with
-// prefill.hip and documented there. This file owns the strided, unguarded
-// global loads with register prefetch of the next tile, the causal tile
-// bound and wave skip, and the lse store.
 //
 // Backward (attn_bwd_keylane_kernel; one workgroup = 4 waves = 256 keys of
 // one (batch, kv head), each wave owning 64 keys, all waves walking all
@@ -25,133 +19,6 @@
 
 #include "attn_tile.h"
 #include "hip_common.h"
-
-namespace {
-
-template <int HD>
-__global__ __launch_bounds__(256, 1) void attn_fwd_kernel(
-    const short* __restrict__ qg, const short* __restrict__ kg,
-    const short* __restrict__ vg, short* __restrict__ og, float* __restrict__ lseg,
-    int B, int Hq, int Hkv, int S, float scale, bool causal,
-    long long q_sb, long long q_sh, long long q_ss,  // q/o strides (elements)
-    long long kv_sb, long long kv_sh, long long kv_ss) {
-  constexpr int KC = HD / 16;        // 16-wide k chunks over head dim
-  constexpr int DBLK = HD / 32;      // 32-row d blocks
-  __shared__ __attribute__((aligned(16))) short k_lds[KVB * HD];
-  __shared__ __attribute__((aligned(16))) short vt_lds[HD * VT_PITCH];
-  __shared__ __attribute__((aligned(16))) short ot_lds[NWAVE][QB * (HD + 8)];  // epilogue transpose
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int hi = lane >> 5;  // half-wave
-  const int ln = lane & 31;
-
-  const int bh = blockIdx.y;
-  const int b = bh / Hq;
-  const int hq = bh % Hq;
-  const int hkv = hq / (Hq / Hkv);
-  const long long qbase = (long long)b * q_sb + (long long)hq * q_sh;
-  const long long kvbase = (long long)b * kv_sb + (long long)hkv * kv_sh;
-
-  const int q0wg = blockIdx.x * WGQ;
-  const int q0 = q0wg + wid * QB;   // this wave's q rows
-  const int qrow = q0 + ln;         // this lane's q row (its S^T column)
-  const int vis = causal ? qrow : INT_MAX;  // last kv index this row may see
-
-  // ---- Q fragments: B operand of S^T = mfma(K, Q); lane ln = q column ----
-  s16x8 qfrag[KC];
-#pragma unroll
-  for (int kc = 0; kc < KC; ++kc)
-    qfrag[kc] = *reinterpret_cast<const s16x8*>(qg + qbase + (long long)qrow * q_ss +
-                                                16 * kc + 8 * hi);
-
-  f32x16 ot[DBLK] = {};
-  float m_run = -INFINITY, l_run = 0.f;
-
-  // ---- register-staged K/V prefetch (guide T14: issue the next tile's
-  // global loads before computing the current one; HBM latency hides under
-  // the MFMA phase instead of stalling every wave at the staging barrier) --
-  s16x8 kreg[ATTN_KCH<HD>];
-  s16x8 vreg[ATTN_VCH<HD>];
-  auto load_tile = [&](int kv0) {
-#pragma unroll
-    for (int c = 0; c < ATTN_KCH<HD>; ++c)
-      kreg[c] = *reinterpret_cast<const s16x8*>(
-          kg + kvbase + (long long)(kv0 + attn_k_row<HD>(c, tid)) * kv_ss +
-          attn_k_e0<HD>(c, tid));
-#pragma unroll
-    for (int i = 0; i < ATTN_VCH<HD>; ++i)
-      vreg[i] = *reinterpret_cast<const s16x8*>(
-          vg + kvbase + (long long)(kv0 + attn_v_row(tid)) * kv_ss + attn_v_e0(i, tid));
-  };
-
-  const int kv_end = causal ? (q0wg + WGQ) : S;  // exclusive upper bound
-  load_tile(0);
-  for (int kv0 = 0; kv0 < kv_end; kv0 += KVB) {
-    __syncthreads();  // previous tile's LDS consumers done
-    attn_write_tile<HD>(k_lds, vt_lds, tid, kreg, vreg);
-    if (kv0 + KVB < kv_end) load_tile(kv0 + KVB);  // prefetch next tile
-    __syncthreads();  // this tile's LDS image ready
-
-    if (causal && kv0 > q0 + QB - 1) continue;  // wave fully above the diagonal
-    attn_tile_step<HD>(k_lds, vt_lds, qfrag, ot, m_run, l_run, kv0, scale, vis);
-  }
-
-  if (lane < 32) lseg[(long long)bh * S + qrow] = m_run + __logf(fmaxf(l_run, 1e-30f));
-  attn_store_o<HD>(ot, l_run, ot_lds[wid], og + qbase, q_ss, q0, S);
-}
-
-}  // namespace
-
-// layout: "bhsd" = [B,H,S,D] contiguous; "bshd" = [B,S,H,D] contiguous
-// (the model's natural projection layout — no transpose copies needed).
-std::vector<torch::Tensor> attn_fwd_ex(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                                       bool causal, const std::string& layout) {
-  TORCH_CHECK(q.dim() == 4 && q.dtype() == torch::kBFloat16 && q.is_contiguous());
-  const bool bshd = layout == "bshd";
-  const int B = q.size(0);
-  const int Hq = bshd ? q.size(2) : q.size(1);
-  const int S = bshd ? q.size(1) : q.size(2);
-  const int HD = q.size(3);
-  const int Hkv = bshd ? k.size(2) : k.size(1);
-  TORCH_CHECK(Hq % Hkv == 0 && (HD == 64 || HD == 128));
-  TORCH_CHECK(S % WGQ == 0, "seq len must be a multiple of 128");
-  auto o = torch::empty_like(q);
-  auto lse = torch::empty({B, Hq, S}, q.options().dtype(torch::kFloat32));
-  const float scale = 1.0f / sqrtf((float)HD);
-  dim3 grid(S / WGQ, B * Hq);
-  hipStream_t stream = hypha_stream();
-  long long q_sb, q_sh, q_ss, kv_sb, kv_sh, kv_ss;
-  if (bshd) {
-    q_sh = HD; q_ss = (long long)Hq * HD; q_sb = (long long)S * Hq * HD;
-    kv_sh = HD; kv_ss = (long long)Hkv * HD; kv_sb = (long long)S * Hkv * HD;
-  } else {
-    q_ss = HD; q_sh = (long long)S * HD; q_sb = (long long)Hq * S * HD;
-    kv_ss = HD; kv_sh = (long long)S * HD; kv_sb = (long long)Hkv * S * HD;
-  }
-#define LAUNCH_FWD(HDV)                                                                 \
-  hipLaunchKernelGGL(attn_fwd_kernel<HDV>, grid, dim3(256), 0, stream,                  \
-                     (const short*)q.data_ptr(), (const short*)k.data_ptr(),            \
-                     (const short*)v.data_ptr(), (short*)o.data_ptr(),                  \
-                     lse.data_ptr<float>(), B, Hq, Hkv, S, scale, causal, q_sb, q_sh,   \
-                     q_ss, kv_sb, kv_sh, kv_ss)
-  if (HD == 128)
-    LAUNCH_FWD(128);
-  else
-    LAUNCH_FWD(64);
-#undef LAUNCH_FWD
-  return {o, lse};
-}
-
-std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                                    bool causal) {
-  return attn_fwd_ex(q, k, v, causal, "bhsd");
-}
-
-// ===========================================================================
-// Backward
-// ===========================================================================
 
 namespace {
 
@@ -198,48 +65,14 @@ __global__ void cast_f32_to_bf16_kernel(const float* __restrict__ in,
   }
 }
 
-// ---- LDS images of the backward kernel ------------------------------------
-// Byte offset of element `elem` of row `row` in a [rows][HD] bf16 image laid
-// out as 8-row x 32-column subtiles of 512 B whose 16-byte chunks are XORed
-// with (row >> 2) & 3: one image serves 16-byte row reads and
-// ds_read_b64_tr_b16 column reads, and the 32x32x16 operand reads of a
-// 32-row tile need two address registers of each kind, the rest being
-// constants (the kernel's rd_base / tr_base / trk_base spell those out; this
-// function is the definition they follow). The XOR moves 16-byte chunks, so a
-// lane's 8-byte piece of a transposed read is not at base + 8 * p.
-template <int HD>
-__device__ __forceinline__ int img_off(int row, int elem) {
-  const int ch = elem >> 3;
-  return (HD / 32) * 512 * (row >> 3) + 512 * (ch >> 2) + 64 * (row & 7) +
-         16 * ((ch & 3) ^ ((row >> 2) & 3)) + 2 * (elem & 7);
-}
+// ---- LDS images of the backward kernel: img_off, lds_tr_pair and acc_frag
+// are attn_tile.h's, shared with the forward ---------------------------------
 
 // dS image [key][32 q] bf16, 64-byte rows, addressed in 8-byte units of 4 q
 // rows; the unit index is XORed with (key >> 2) & 7 so that the 32 lanes of
 // a half (32 keys, one unit each) store to 32 distinct bank pairs.
 __device__ __forceinline__ int ds_off(int key, int unit) {
   return key * 64 + ((unit ^ ((key >> 2) & 7)) << 3);
-}
-
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-// Two ds_read_b64_tr_b16 (4 rows x 16 columns each, delivered column-major)
-// joined into one 8-element MFMA fragment.
-__device__ __forceinline__ s16x8 lds_tr_pair(const short* img, int off0, int off1) {
-  s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)((char*)img + off0));
-  s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)((char*)img + off1));
-  return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-// Registers 8s .. 8s+7 of a 32x32 accumulator as the bf16 fragment of k-step
-// s of a following MFMA that sums over the accumulator's rows. Element j of
-// lane half h is row 16s + 8(j>>2) + 4h + (j&3): the other operand must be
-// read in that k order (tr_a_off below does).
-__device__ __forceinline__ s16x8 acc_frag(const f32x16& x, int s) {
-  unsigned w[4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m) w[m] = pack_bf16x2(x[8 * s + 2 * m], x[8 * s + 2 * m + 1]);
-  return *reinterpret_cast<s16x8*>(w);
 }
 
 // Backward, key on the lane. (v2, v3 and v4 are the removed earlier

@@ -76,6 +76,7 @@ std::vector<torch::Tensor> attn_bwd_ex(torch::Tensor q, torch::Tensor k, torch::
 torch::Tensor mfma_probe_32x32x16(torch::Tensor a, torch::Tensor b);
 torch::Tensor mfma_probe_16x16x32(torch::Tensor a, torch::Tensor b);
 torch::Tensor mfma_probe_acc_operand(torch::Tensor a, torch::Tensor m1, torch::Tensor m2);
+torch::Tensor mfma_probe_tr_v_operand(torch::Tensor v, torch::Tensor m1, torch::Tensor m2);
 // fp8_cast.hip
 std::vector<torch::Tensor> fp8_cast_transpose(torch::Tensor x, torch::Tensor scale,
                                               torch::Tensor partials, long skip_t);
@@ -186,6 +187,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_probe_32x32x16", &mfma_probe_32x32x16);
   m.def("mfma_probe_16x16x32", &mfma_probe_16x16x32);
   m.def("mfma_probe_acc_operand", &mfma_probe_acc_operand);
+  m.def("mfma_probe_tr_v_operand", &mfma_probe_tr_v_operand);
   m.def("fp8_cast_transpose", &fp8_cast_transpose, pybind11::arg("x"),
         pybind11::arg("scale"), pybind11::arg("partials"),
         pybind11::arg("skip_t") = 0);

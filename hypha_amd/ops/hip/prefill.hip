@@ -65,8 +65,8 @@ __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
     const int* __restrict__ block_table, int max_pages, int n_pages) {
   constexpr int KC = HD / 16;        // 16-wide k chunks over head dim
   constexpr int DBLK = HD / 32;      // 32-row d blocks
-  __shared__ __attribute__((aligned(16))) short k_lds[KVB * HD];
-  __shared__ __attribute__((aligned(16))) short vt_lds[HD * VT_PITCH];
+  __shared__ __attribute__((aligned(16))) short k_img[KVB * HD];
+  __shared__ __attribute__((aligned(16))) short v_img[KVB * HD];
   __shared__ __attribute__((aligned(16))) short ot_lds[NWAVE][QB * (HD + 8)];  // epilogue transpose
 
   const int tid = threadIdx.x;
@@ -98,28 +98,31 @@ __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
   // exclusive kv bound of this workgroup: >= 1, <= len_b <= T_alloc
   const int kv_end = min(len_b, pos + q0wg + WGQ);
 
-  // ---- Q fragments: B operand of S^T = mfma(K, Q); lane ln = q column ----
-  s16x8 qfrag[KC];
+  // ---- Q fragments: B operand of S^T = mfma(K, Q); lane ln = q column.
+  // One head per wave (attn_tile_step's G = 1) ----
+  s16x8 qfrag[1][KC];
 #pragma unroll
   for (int kc = 0; kc < KC; ++kc) {
     s16x8 qv = {};
     if (qrow < s_b)
       qv = *reinterpret_cast<const s16x8*>(qg + qbase + (long long)qrow * q_ss +
                                            16 * kc + 8 * hi);
-    qfrag[kc] = qv;
+    qfrag[0][kc] = qv;
   }
 
-  f32x16 ot[DBLK] = {};
-  float m_run = -INFINITY, l_run = 0.f;
+  f32x16 ot[1][DBLK] = {};
+  float m_run[1] = {-INFINITY}, l_run[1] = {0.f};
+  const AttnLaneOffs lo = attn_lane_offs(DBLK * 512);
+  const float c2 = 1.4426950408889634f * scale;  // exp(scale*x) = exp2(c2*x)
 
   // ---- register-staged K/V prefetch: the next tile's global loads are
   // issued before the current tile's MFMA phase. fp8 mode keeps the raw
   // bytes + row scale in registers and converts at the LDS write, so the
   // conversion does not wait on the loads it was meant to hide ----
-  constexpr int KCH = ATTN_KCH<HD>, VCH = ATTN_VCH<HD>;  // 8-elem chunks per thread
-  s16x8 kreg[KCH], vreg[VCH];  // bf16 chunks (fp8 mode: filled at the LDS write)
-  uint2 kraw[KCH], vraw[VCH];  // fp8 mode: raw bytes
-  float ksc[KCH], vsc = 0.f;   // fp8 mode: row scales
+  constexpr int CH = ATTN_CH<HD>;  // 8-elem chunks per thread, of K and of V
+  s16x8 kreg[CH], vreg[CH];  // bf16 chunks (fp8 mode: filled at the LDS write)
+  uint2 kraw[CH], vraw[CH];  // fp8 mode: raw bytes
+  float ksc[CH], vsc[CH];    // fp8 mode: row scales
   auto load_tile = [&](int kv0) {
     // paged: pool row index of this tile's row 0 (kv0 < kv_end <= max_pages * KVB)
     long long prow0 = 0;
@@ -128,59 +131,44 @@ __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
       prow0 = (long long)min(max(page, 0), n_pages - 1) * KVB;
     }
 #pragma unroll
-    for (int c = 0; c < KCH; ++c) {
-      const int row = attn_k_row<HD>(c, tid), e0 = attn_k_e0<HD>(c, tid);
+    for (int c = 0; c < CH; ++c) {
+      const int row = attn_ch_row<HD>(c, tid), e0 = attn_ch_e0<HD>(tid);
       const bool ok = kv0 + row < kv_end;
       const long long srow =
           PAGED ? (prow0 + row) * Hkv + hkv : (kvrow0 + kv0 + row) * Hkv + hkv;
       if (QUANT) {
-        kraw[c] = make_uint2(0u, 0u);
-        ksc[c] = 0.f;
+        kraw[c] = vraw[c] = make_uint2(0u, 0u);
+        ksc[c] = vsc[c] = 0.f;
         if (ok) {
           kraw[c] = *reinterpret_cast<const uint2*>(
               reinterpret_cast<const unsigned char*>(kgv) + srow * HD + e0);
+          vraw[c] = *reinterpret_cast<const uint2*>(
+              reinterpret_cast<const unsigned char*>(vgv) + srow * HD + e0);
           ksc[c] = kscale[srow];
+          vsc[c] = vscale[srow];
         }
       } else {
-        s16x8 kv8 = {};
-        if (ok)
-          kv8 = *reinterpret_cast<const s16x8*>(
+        s16x8 k8 = {}, v8 = {};
+        if (ok) {
+          k8 = *reinterpret_cast<const s16x8*>(
               reinterpret_cast<const short*>(kgv) + srow * HD + e0);
-        kreg[c] = kv8;
-      }
-    }
-    {
-      const int kvr = attn_v_row(tid);
-      const bool ok = kv0 + kvr < kv_end;
-      const long long srow =
-          PAGED ? (prow0 + kvr) * Hkv + hkv : (kvrow0 + kv0 + kvr) * Hkv + hkv;
-      if (QUANT) vsc = ok ? vscale[srow] : 0.f;
-#pragma unroll
-      for (int i = 0; i < VCH; ++i) {
-        const int e0 = attn_v_e0(i, tid);
-        if (QUANT) {
-          vraw[i] = make_uint2(0u, 0u);
-          if (ok)
-            vraw[i] = *reinterpret_cast<const uint2*>(
-                reinterpret_cast<const unsigned char*>(vgv) + srow * HD + e0);
-        } else {
-          s16x8 v8 = {};
-          if (ok)
-            v8 = *reinterpret_cast<const s16x8*>(
-                reinterpret_cast<const short*>(vgv) + srow * HD + e0);
-          vreg[i] = v8;
+          v8 = *reinterpret_cast<const s16x8*>(
+              reinterpret_cast<const short*>(vgv) + srow * HD + e0);
         }
+        kreg[c] = k8;
+        vreg[c] = v8;
       }
     }
   };
   auto write_tile = [&]() {
     if (QUANT) {
 #pragma unroll
-      for (int c = 0; c < KCH; ++c) kreg[c] = dequant8(kraw[c], ksc[c]);
-#pragma unroll
-      for (int i = 0; i < VCH; ++i) vreg[i] = dequant8(vraw[i], vsc);
+      for (int c = 0; c < CH; ++c) {
+        kreg[c] = dequant8(kraw[c], ksc[c]);
+        vreg[c] = dequant8(vraw[c], vsc[c]);
+      }
     }
-    attn_write_tile<HD>(k_lds, vt_lds, tid, kreg, vreg);
+    attn_write_tile<HD>(k_img, v_img, tid, kreg, vreg);
   };
 
   load_tile(0);
@@ -195,13 +183,18 @@ __global__ __launch_bounds__(256, 1) void attn_prefill_kernel(
     // is visible to every row (vis >= 0): attn_tile_step's m_run is finite
     // from the first processed tile on.
     if (!wave_live || kv0 > pos + q0 + QB - 1) continue;
-    attn_tile_step<HD>(k_lds, vt_lds, qfrag, ot, m_run, l_run, kv0, scale, vis);
+    // the masked body only where the tile reaches past what the wave's first
+    // row sees; every lane's vis is at least that
+    if (kv0 + KVB - 1 > min(pos + q0, len_b - 1))
+      attn_tile_step<HD, 1, true>(k_img, v_img, lo, qfrag, ot, m_run, l_run, kv0, c2, vis);
+    else
+      attn_tile_step<HD, 1, false>(k_img, v_img, lo, qfrag, ot, m_run, l_run, kv0, c2, vis);
   }
 
   if (!wave_live) return;  // no barrier below this point
 
   // only the rows < s_b are stored
-  attn_store_o<HD>(ot, l_run, ot_lds[wid], og + qbase, q_ss, q0, s_b);
+  attn_store_o<HD>(ot[0], l_run[0], ot_lds[wid], og + qbase, q_ss, q0, s_b);
 }
 
 torch::Tensor attn_prefill_impl(torch::Tensor q, torch::Tensor kcache,

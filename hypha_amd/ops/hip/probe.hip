@@ -12,6 +12,7 @@
 
 #include <torch/extension.h>
 
+#include "attn_tile.h"
 #include "hip_common.h"
 
 __global__ void probe32_kernel(const short* __restrict__ a, const short* __restrict__ b,
@@ -88,6 +89,48 @@ __global__ void probe_acc_operand_kernel(const short* __restrict__ a,
   for (int r = 0; r < 16; ++r) y[((r & 3) + 8 * (r >> 2) + 4 * h) * 32 + n] = acc[r];
 }
 
+// The forward's O^T += V^T P^T as attn_tile.h runs it: P^T = M1 * M2 (64x16 by
+// 16x32, kv rows in registers, q on the lane) stays in two accumulators and is
+// packed by acc_frag; V [64 kv][64 d] is staged row-major through img_off and
+// read by columns (attn_pv: ds_read_b64_tr_b16 at AttnLaneOffs::tr) in
+// acc_frag's permuted k order. Y = V^T * P^T, [64 d][32 q].
+__global__ void probe_tr_v_operand_kernel(const short* __restrict__ v,
+                                          const short* __restrict__ m1,
+                                          const short* __restrict__ m2,
+                                          float* __restrict__ y) {
+  constexpr int HD = 64;
+  __shared__ __attribute__((aligned(16))) short v_img[KVB * HD];
+  const int l = threadIdx.x;  // one wave
+  const int h = l >> 5, n = l & 31;
+  for (int c = l; c < KVB * HD / 8; c += 64) {
+    const int row = c / (HD / 8), e0 = (c % (HD / 8)) * 8;
+    *reinterpret_cast<s16x8*>((char*)v_img + img_off<HD>(row, e0)) =
+        *reinterpret_cast<const s16x8*>(v + row * HD + e0);
+  }
+  __syncthreads();
+  s16x8 pf[1][4];
+#pragma unroll
+  for (int mb = 0; mb < 2; ++mb) {
+    s16x8 af, bf;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      af[j] = m1[(32 * mb + n) * 16 + 8 * h + j];
+      bf[j] = m2[(8 * h + j) * 32 + n];
+    }
+    f32x16 x = {};
+    x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf, x, 0, 0, 0);
+    pf[0][2 * mb] = acc_frag<true>(x, 0);
+    pf[0][2 * mb + 1] = acc_frag<true>(x, 1);
+  }
+  f32x16 ot[1][HD / 32] = {};
+  attn_pv<HD, 1>(v_img, attn_lane_offs((HD / 32) * 512), pf, ot);
+#pragma unroll
+  for (int db = 0; db < HD / 32; ++db)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      y[(32 * db + (r & 3) + 8 * (r >> 2) + 4 * h) * 32 + n] = ot[0][db][r];
+}
+
 torch::Tensor mfma_probe_32x32x16(torch::Tensor a, torch::Tensor b) {
   TORCH_CHECK(a.sizes() == torch::IntArrayRef({32, 16}) &&
               b.sizes() == torch::IntArrayRef({16, 32}));
@@ -119,6 +162,20 @@ torch::Tensor mfma_probe_acc_operand(torch::Tensor a, torch::Tensor m1, torch::T
   auto y = torch::empty({32, 32}, a.options().dtype(torch::kFloat32));
   hipLaunchKernelGGL(probe_acc_operand_kernel, dim3(1), dim3(64), 0, hypha_stream(),
                      (const short*)a.data_ptr(), (const short*)m1.data_ptr(),
+                     (const short*)m2.data_ptr(), y.data_ptr<float>());
+  return y;
+}
+
+torch::Tensor mfma_probe_tr_v_operand(torch::Tensor v, torch::Tensor m1, torch::Tensor m2) {
+  auto ok = [](const torch::Tensor& t, int r, int c) {
+    return t.is_cuda() && t.dtype() == torch::kBFloat16 && t.is_contiguous() &&
+           t.sizes() == torch::IntArrayRef({r, c});
+  };
+  TORCH_CHECK(ok(v, 64, 64) && ok(m1, 64, 16) && ok(m2, 16, 32),
+              "mfma_probe_tr_v_operand: v [64,64], m1 [64,16], m2 [16,32], bf16 on the GPU");
+  auto y = torch::empty({64, 32}, v.options().dtype(torch::kFloat32));
+  hipLaunchKernelGGL(probe_tr_v_operand_kernel, dim3(1), dim3(64), 0, hypha_stream(),
+                     (const short*)v.data_ptr(), (const short*)m1.data_ptr(),
                      (const short*)m2.data_ptr(), y.data_ptr<float>());
   return y;
 }

@@ -1,7 +1,10 @@
 """Micro-benchmark for the attention kernels at Llama-3-8B shapes.
 
 Usage: python tools/attn_bench.py [--iters N] [--mode fwd|bwd|both]
+                                  [--batch B] [--seq S] [--layout bhsd|bshd]
+                                  [--head-dim 64|128]
 Prints TF/s for forward and backward at B4 Hq32 Hkv8 S2048 D128 (causal).
+The training step runs the bshd layout.
 """
 
 import argparse
@@ -21,19 +24,24 @@ def main():
     p.add_argument("--mode", default="both")
     p.add_argument("--batch", type=int, default=4)
     p.add_argument("--seq", type=int, default=2048)
+    p.add_argument("--layout", default="bhsd", choices=["bhsd", "bshd"])
+    p.add_argument("--head-dim", type=int, default=128, choices=[64, 128])
     args = p.parse_args()
 
     from hypha_amd import _C
 
-    B, Hq, Hkv, S, D = args.batch, 32, 8, args.seq, 128
+    B, Hq, Hkv, S, D = args.batch, 32, 8, args.seq, args.head_dim
     torch.manual_seed(0)
     dev = "cuda:0"
-    q = torch.randn(B, Hq, S, D, device=dev).bfloat16()
-    k = torch.randn(B, Hkv, S, D, device=dev).bfloat16()
-    v = torch.randn(B, Hkv, S, D, device=dev).bfloat16()
-    do = torch.randn(B, Hq, S, D, device=dev).bfloat16()
+    lay = args.layout
 
-    o, lse = _C.attn_fwd(q, k, v, True)
+    def rand(h):
+        shape = (B, h, S, D) if lay == "bhsd" else (B, S, h, D)
+        return torch.randn(*shape, device=dev).bfloat16()
+
+    q, k, v, do = rand(Hq), rand(Hkv), rand(Hkv), rand(Hq)
+
+    o, lse = _C.attn_fwd_ex(q, k, v, True, lay)
 
     # causal flops: QK^T + PV = 2 * 2 * B*Hq*S^2*D / 2 (triangle)
     fwd_flops = 2 * 2 * B * Hq * S * S * D / 2
@@ -50,10 +58,10 @@ def main():
         return (time.perf_counter() - t0) / iters
 
     if args.mode in ("fwd", "both"):
-        t = bench(lambda: _C.attn_fwd(q, k, v, True), args.iters)
+        t = bench(lambda: _C.attn_fwd_ex(q, k, v, True, lay), args.iters)
         print(f"fwd: {t*1e3:.3f} ms  {fwd_flops/t/1e12:.1f} TF/s")
     if args.mode in ("bwd", "both"):
-        t = bench(lambda: _C.attn_bwd(q, k, v, o, do, lse, True), args.iters)
+        t = bench(lambda: _C.attn_bwd_ex(q, k, v, o, do, lse, True, lay), args.iters)
         print(f"bwd: {t*1e3:.3f} ms  {bwd_flops/t/1e12:.1f} TF/s")
 
 
