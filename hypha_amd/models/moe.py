@@ -26,6 +26,9 @@ class MoEConfig(LlamaConfig):
     n_experts: int = 8
     top_k: int = 2
     router_aux_loss_coef: float = 0.01
+    # inference with at most this many tokens takes ops.moe_ffn (0 = never);
+    # the measured crossover at Mixtral widths, profiles/moe_ffn.md
+    fused_ffn_max_tokens: int = 64
 
     def num_params(self) -> int:
         h, v, f = self.hidden_size, self.vocab_size, self.ffn_hidden
@@ -127,6 +130,12 @@ class MoEMLP(nn.Module):
         xf = x.reshape(-1, h)  # [T, h]
         t = xf.shape[0]
         logits = self.router(xf).float()  # [T, E]
+        if self._use_fused_ffn(xf):
+            # inference at decode sizes: routing, grouping and the expert
+            # GEMMs on the device (ops/hip/moe_ffn.hip), no host sync
+            out = ops.moe_ffn(xf.contiguous(), logits, self.w_gate, self.w_up,
+                              self.w_down, cfg.top_k)
+            return out.reshape(b, s, h), xf.new_zeros(())
         probs = torch.softmax(logits, dim=-1)
         topv, topi = probs.topk(cfg.top_k, dim=-1)  # [T, K]
         topv = (topv / topv.sum(-1, keepdim=True)).to(x.dtype)
@@ -186,6 +195,23 @@ class MoEMLP(nn.Module):
         out = torch.zeros_like(xf)
         out.index_add_(0, flat_tok[order], grouped_out * weights)
         return out.reshape(b, s, h), aux
+
+    def _use_fused_ffn(self, xf: torch.Tensor) -> bool:
+        """The fused device-routed path serves bf16 inference on one rank, up
+        to cfg.fused_ffn_max_tokens tokens (the measured crossover against the
+        per-expert library loop, profiles/moe_ffn.md)."""
+        import os
+
+        cfg = self.cfg
+        return (
+            not self.training and not torch.is_grad_enabled() and self.ep is None
+            and os.environ.get("HYPHA_NATIVE_GROUPED", "0") != "1"
+            and xf.shape[0] <= cfg.fused_ffn_max_tokens
+            and xf.dtype == torch.bfloat16 and self.w_gate.dtype == torch.bfloat16
+            and ops.use_native(xf)
+            and ops.moe_ffn_native_shapes(cfg.hidden_size, cfg.ffn_hidden,
+                                          cfg.n_experts, cfg.top_k)
+        )
 
     def _expert_ffn(self, xs: torch.Tensor, counts: list[int]) -> torch.Tensor:
         """Per-expert SwiGLU chains over expert-grouped rows (local shard)."""

@@ -69,6 +69,8 @@ from .interface import (  # noqa: E402
     kv_append_paged,
     layernorm,
     linear_skinny,
+    moe_ffn,
+    moe_ffn_native_shapes,
     philox_uniform,
     rmsnorm,
     sample_token,
@@ -101,4 +103,6 @@ __all__ = [
     "extract_delta",
     "sample_token",
     "philox_uniform",
+    "moe_ffn",
+    "moe_ffn_native_shapes",
 ]

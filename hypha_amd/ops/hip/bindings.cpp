@@ -154,6 +154,11 @@ torch::Tensor skinny_gemm(torch::Tensor x, torch::Tensor w);
 torch::Tensor sample_token(torch::Tensor logits, torch::Tensor u, torch::Tensor temperature,
                            torch::Tensor top_k, torch::Tensor top_p);
 torch::Tensor philox_uniform(torch::Tensor seed, torch::Tensor step, long n);
+// moe_ffn.hip (device-routed top-k expert FFN for inference)
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> moe_route(
+    torch::Tensor router_logits, long top_k);
+torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor router_logits, torch::Tensor w_gate,
+                      torch::Tensor w_up, torch::Tensor w_down, long top_k);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adamw_step_", &adamw_step_);
@@ -216,4 +221,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm", &skinny_gemm);
   m.def("sample_token", &sample_token);
   m.def("philox_uniform", &philox_uniform);
+  m.def("moe_route", &moe_route);
+  m.def("moe_ffn", &moe_ffn);
 }

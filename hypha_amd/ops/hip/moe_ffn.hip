@@ -1,0 +1,453 @@
+// Fused top-k MoE expert FFN for inference (Mixtral-style SwiGLU experts):
+//
+//   out[t] = sum_k w[t,k] * W_down[e] (silu(W_gate[e] x[t]) * (W_up[e] x[t])),
+//   e = topi[t,k], w = renormalised fp32 softmax top-k of the router logits.
+//
+// Routing, grouping, both GEMM stages and the combine run on the device; the
+// host never learns who chose what, so every grid depends on the shapes alone
+// and a captured graph replays correctly under any routing. Five launches:
+//
+//   moe_route_kernel    one wave per token, one lane per expert (E <= 64):
+//                       softmax by wave reductions, top_k rounds of (value,
+//                       lowest index) arg-max on the logits, fp32 renormalise.
+//   moe_group_kernel    stable counting sort of the pair ids p = t*K + k by
+//                       expert, one workgroup: a wave owns an expert and walks
+//                       the pairs in order with ballots, so counts and
+//                       positions are fixed-order (no atomics at all).
+//   moe_expert_kernel<false>  gate/up: grid (f/32, E). hbuf[p, f] = bf16(
+//                       silu(g) * u) from fp32 accumulators.
+//   moe_expert_kernel<true>   down: grid (h/64, E, splits). ybuf[s, p, h] =
+//                       fp32 partial * w[p].
+//   moe_combine_kernel  out[t] = bf16(sum_k sum_s ybuf[s, t*K+k]) in a fixed
+//                       order. No float atomics anywhere: same bits every run.
+//
+// moe_expert_kernel is a weight-streaming kernel, not a throughput GEMM. A
+// workgroup whose expert received no pair returns before its first weight
+// load and its first barrier, so at T = 1 only top_k of the E experts are
+// read. A live workgroup owns two 32-row weight tiles (gate and up rows of
+// one f tile; or two adjacent h tiles of W_down) and streams them from global
+// memory once, straight into registers as the A operand of
+// v_mfma_f32_32x32x16_bf16 (weight rows on M). The expert's gathered
+// activation rows are the B operand (tokens on N, 32 at a time), staged
+// through LDS in chunks of 256 k, double buffered, one barrier per chunk.
+// The four waves split every chunk by k: wave w takes k in [64 w, 64 w + 64),
+// i.e. one whole 128-byte line of each of its 64 weight rows, fetched by four
+// 16-byte loads per lane per tile (lane (m, hi) of MFMA step j reads k =
+// 16 j + 8 hi .. + 8: the natural order, which A and B share). The next
+// chunk's 8 weight loads and 4 activation loads per lane are issued before the
+// current chunk's MFMAs, so a wave keeps 12 KiB in flight. The waves' partial
+// accumulators meet in LDS (aliasing the staging buffers) in wave order.
+// An expert with more than 32 pairs loops over token tiles and re-reads its
+// weight tile from L2; columns past the count are zero in LDS and never
+// stored.
+
+#include <torch/extension.h>
+
+#include <tuple>
+
+#include "hip_common.h"
+
+namespace {
+
+constexpr int kMaxExperts = 64;
+constexpr int kMaxTopK = 8;
+constexpr int NT = 32;          // tokens per MFMA N tile
+constexpr int KC = 256;         // k per LDS chunk: 4 waves x 64
+constexpr int PITCH = KC + 8;   // LDS row pitch (528 B: conflict-free b128 reads)
+constexpr int kGroupThreads = 1024;
+
+// ---- routing ----------------------------------------------------------------
+
+__global__ __launch_bounds__(64) void moe_route_kernel(
+    const float* __restrict__ logits, int* __restrict__ topi, float* __restrict__ topw,
+    int E, int K) {
+  const int t = blockIdx.x, lane = threadIdx.x;
+  float l = -INFINITY;
+  if (lane < E) {
+    l = logits[(long long)t * E + lane];
+    if (!(l == l)) l = -INFINITY;  // NaN never wins
+  }
+  const float mx = wave_reduce_max(l);
+  const float p = (lane < E && l > -INFINITY) ? expf(l - mx) : 0.f;
+  const float prob = p / wave_reduce_sum(p);
+
+  bool taken = lane >= E;
+  int sel[kMaxTopK];
+  float val[kMaxTopK];
+  float denom = 0.f;
+#pragma unroll
+  for (int k = 0; k < kMaxTopK; ++k) {  // constant bound: sel/val stay in registers
+    if (k >= K) break;
+    // arg-max of (logit, lowest index) over the lanes not yet taken; taken
+    // lanes rank below every free lane, whatever their value
+    float v = taken ? -INFINITY : l;
+    int i = taken ? 64 + lane : lane;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float vo = __shfl_xor(v, off, 64);
+      const int io = __shfl_xor(i, off, 64);
+      if (vo > v || (vo == v && io < i)) {
+        v = vo;
+        i = io;
+      }
+    }
+    i &= 63;
+    if (lane == i) taken = true;
+    sel[k] = i;
+    val[k] = __shfl(prob, i, 64);
+    denom += val[k];
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < kMaxTopK; ++k) {
+      if (k >= K) break;
+      topi[(long long)t * K + k] = sel[k];
+      topw[(long long)t * K + k] = val[k] / denom;
+    }
+  }
+}
+
+// Stable counting sort of the pair ids by expert. Wave w owns experts w,
+// w + 16, ...; for each it walks all pairs in ascending order, 64 at a time:
+// the count is a sum of ballot popcounts and a pair's position is the count
+// before it plus the matching lanes below it.
+__global__ __launch_bounds__(kGroupThreads) void moe_group_kernel(
+    const int* __restrict__ topi, int* __restrict__ offsets, int* __restrict__ pairs,
+    int P, int E) {
+  __shared__ int s_cnt[kMaxExperts];
+  __shared__ int s_off[kMaxExperts + 1];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  constexpr int kWaves = kGroupThreads / 64;
+  for (int e = wid; e < E; e += kWaves) {
+    int c = 0;
+    for (int i = 0; i < P; i += 64) {
+      const int idx = i + lane;
+      const bool m = idx < P && topi[idx] == e;
+      c += __popcll(__ballot(m));
+    }
+    if (lane == 0) s_cnt[e] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int run = 0;
+    for (int e = 0; e < E; ++e) {
+      s_off[e] = run;
+      offsets[e] = run;
+      run += s_cnt[e];
+    }
+    s_off[E] = run;
+    offsets[E] = run;
+  }
+  __syncthreads();
+  for (int e = wid; e < E; e += kWaves) {
+    int base = s_off[e];
+    for (int i = 0; i < P; i += 64) {
+      const int idx = i + lane;
+      const bool m = idx < P && topi[idx] == e;
+      const unsigned long long mask = __ballot(m);
+      if (m) pairs[base + __popcll(mask & ((1ull << lane) - 1ull))] = idx;
+      base += __popcll(mask);
+    }
+  }
+}
+
+// ---- expert GEMMs -------------------------------------------------------------
+
+// DOWN = false: act = x [T, Kd], wa/wb = W_gate/W_up [E, R, Kd], 32-row tiles,
+//               out = hbuf bf16 [P, R].
+// DOWN = true : act = hbuf [P, Kd], wa = W_down [E, R, Kd], 64-row tiles,
+//               out = ybuf fp32 [gridDim.z, P, R]; split z takes the chunks
+//               [z * cps, (z + 1) * cps).
+template <bool DOWN>
+__global__ __launch_bounds__(256, 3) void moe_expert_kernel(
+    const short* __restrict__ act, const short* __restrict__ wa,
+    const short* __restrict__ wb, const int* __restrict__ offsets,
+    const int* __restrict__ pairs, const float* __restrict__ topw,
+    void* __restrict__ outp, int Kd, int R, int top_k, int P, int cps) {
+  const int e = blockIdx.y;
+  const int off = offsets[e];
+  const int cnt = offsets[e + 1] - off;
+  if (cnt == 0) return;  // nobody chose this expert: no weight is read
+
+  __shared__ __attribute__((aligned(16))) short xs[2 * NT * PITCH];
+  float* red = reinterpret_cast<float*>(xs);  // [4 waves][2 tiles][16][64] after the k loop
+  static_assert(4 * 2 * 16 * 64 * sizeof(float) <= sizeof(short) * 2 * NT * PITCH,
+                "reduction image must fit the staging buffers");
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, w = tid >> 6;
+  const int ln = lane & 31, hi = lane >> 5;
+  const int rows0 = blockIdx.x * (DOWN ? 64 : 32);
+  const short* a0 = wa + ((long long)e * R + rows0 + ln) * Kd + 8 * hi;
+  const short* a1 = DOWN ? a0 + 32ll * Kd
+                         : wb + ((long long)e * R + rows0 + ln) * Kd + 8 * hi;
+  const int nc = (Kd + KC - 1) / KC;
+  const int c0 = blockIdx.z * cps;
+  const int c1 = min(nc, c0 + cps);
+  const int xslot = tid >> 5;        // staging: slots xslot + 8 i, i < 4
+  const int xk = (tid & 31) * 8;     // k inside the chunk
+
+  for (int t0 = 0; t0 < cnt; t0 += NT) {
+    int rowi[4];  // activation row of each staged slot, -1 past the count
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int s = t0 + xslot + 8 * i;
+      rowi[i] = -1;
+      if (s < cnt) rowi[i] = DOWN ? pairs[off + s] : pairs[off + s] / top_k;
+    }
+    auto load_x = [&](int c, s16x8(&xr)[4]) {
+      const int k = c * KC + xk;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        xr[i] = s16x8{};
+        if (rowi[i] >= 0 && k < Kd)
+          xr[i] = *reinterpret_cast<const s16x8*>(act + (long long)rowi[i] * Kd + k);
+      }
+    };
+    auto store_x = [&](int buf, const s16x8(&xr)[4]) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        *reinterpret_cast<s16x8*>(xs + buf * NT * PITCH + (xslot + 8 * i) * PITCH + xk) =
+            xr[i];
+    };
+    // this wave's 64 k of chunk c: one 128-byte line of each weight row
+    auto load_w = [&](int c, s16x8(&wr)[2][4]) {
+      const int kb = c * KC + w * 64;
+      if (kb < Kd) {  // Kd % 128 == 0, so a started line is whole
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          wr[0][j] = *reinterpret_cast<const s16x8*>(a0 + kb + 16 * j);
+          wr[1][j] = *reinterpret_cast<const s16x8*>(a1 + kb + 16 * j);
+        }
+      }
+    };
+
+    f32x16 acc0 = {}, acc1 = {};
+    s16x8 wcur[2][4] = {}, wnxt[2][4] = {}, xr[4];
+    load_x(c0, xr);
+    load_w(c0, wcur);
+    store_x(0, xr);
+    __syncthreads();
+    for (int c = c0; c < c1; ++c) {
+      const int buf = (c - c0) & 1;
+      const bool more = c + 1 < c1;
+      if (more) {
+        load_x(c + 1, xr);
+        load_w(c + 1, wnxt);
+      }
+      if (c * KC + w * 64 < Kd) {
+        const short* bp = xs + buf * NT * PITCH + ln * PITCH + w * 64 + 8 * hi;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const s16x8 b = *reinterpret_cast<const s16x8*>(bp + 16 * j);
+          acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wcur[0][j], b, acc0, 0, 0, 0);
+          acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wcur[1][j], b, acc1, 0, 0, 0);
+        }
+      }
+      if (more) store_x(buf ^ 1, xr);
+      __syncthreads();
+      if (more) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          wcur[0][j] = wnxt[0][j];
+          wcur[1][j] = wnxt[1][j];
+        }
+      }
+    }
+
+    // the four waves' partial sums meet in LDS and are added in wave order
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      red[((w * 2 + 0) * 16 + r) * 64 + lane] = acc0[r];
+      red[((w * 2 + 1) * 16 + r) * 64 + lane] = acc1[r];
+    }
+    __syncthreads();
+    // thread (n, q): token n, tile rows 8 (q >> 1) + 4 (q & 1) .. + 4, which
+    // are registers 4 (q >> 1) .. + 4 of MFMA lane 32 (q & 1) + n
+    const int n = tid & 31, q = tid >> 5;
+    float s0[4], s1[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = 4 * (q >> 1) + i, src = 32 * (q & 1) + n;
+      s0[i] = 0.f;
+      s1[i] = 0.f;
+#pragma unroll
+      for (int ww = 0; ww < 4; ++ww) {
+        s0[i] += red[((ww * 2 + 0) * 16 + r) * 64 + src];
+        s1[i] += red[((ww * 2 + 1) * 16 + r) * 64 + src];
+      }
+    }
+    if (t0 + n < cnt) {
+      const int p = pairs[off + t0 + n];
+      const int m = 8 * (q >> 1) + 4 * (q & 1);
+      if (!DOWN) {
+        s16x4 o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          o[i] = f2bf(s0[i] / (1.f + __expf(-s0[i])) * s1[i]);
+        *reinterpret_cast<s16x4*>(static_cast<short*>(outp) + (long long)p * R + rows0 + m) = o;
+      } else {
+        const float wt = topw[p];
+        float* y = static_cast<float*>(outp) + ((long long)blockIdx.z * P + p) * R + rows0 + m;
+        f32x4 y0, y1;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          y0[i] = s0[i] * wt;
+          y1[i] = s1[i] * wt;
+        }
+        *reinterpret_cast<f32x4*>(y) = y0;
+        *reinterpret_cast<f32x4*>(y + 32) = y1;
+      }
+    }
+    __syncthreads();  // red aliases the next token tile's staging buffers
+  }
+}
+
+// out[t, c .. c + 8] = bf16(sum_k (sum_s ybuf[s, t K + k, c .. c + 8]))
+__global__ __launch_bounds__(256) void moe_combine_kernel(
+    const float* __restrict__ ybuf, short* __restrict__ out, long long n_vec, int h,
+    int K, int S, long long P) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n_vec) return;
+  const int hv = h / 8;
+  const long long t = idx / hv;
+  const int c = (int)(idx % hv) * 8;
+  float acc[8] = {};
+  for (int k = 0; k < K; ++k) {
+    float part[8] = {};
+    for (int s = 0; s < S; ++s) {
+      const float* y = ybuf + ((long long)s * P + t * K + k) * h + c;
+      const f32x4 lo = *reinterpret_cast<const f32x4*>(y);
+      const f32x4 hi = *reinterpret_cast<const f32x4*>(y + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        part[j] += lo[j];
+        part[4 + j] += hi[j];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] += part[j];
+  }
+  s16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = f2bf(acc[j]);
+  *reinterpret_cast<s16x8*>(out + t * h + c) = o;
+}
+
+// ---- host ---------------------------------------------------------------------
+
+struct Routing {
+  torch::Tensor topi, topw, offsets, pairs;
+};
+
+void check_router(const torch::Tensor& logits, long top_k) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.dtype() == torch::kFloat32 &&
+                  logits.is_contiguous(),
+              "moe: router_logits must be contiguous fp32 [T, E] on the GPU");
+  const long long E = logits.size(1);
+  TORCH_CHECK(E >= 1 && E <= kMaxExperts, "moe: E must lie in [1, 64]");
+  TORCH_CHECK(top_k >= 1 && top_k <= E && top_k <= kMaxTopK,
+              "moe: top_k must lie in [1, min(E, 8)]");
+  TORCH_CHECK(logits.size(0) * top_k < (1ll << 30), "moe: T * top_k out of range");
+}
+
+// T > 0. Routing buffers come from the caching allocator on the current
+// stream (graph-safe); the grids depend on (T, E, K) alone.
+Routing route(const torch::Tensor& logits, int K, hipStream_t stream) {
+  const int T = (int)logits.size(0), E = (int)logits.size(1);
+  const auto i32 = logits.options().dtype(torch::kInt32);
+  Routing r;
+  r.topi = torch::empty({T, K}, i32);
+  r.topw = torch::empty({T, K}, logits.options());
+  r.offsets = torch::empty({E + 1}, i32);
+  r.pairs = torch::empty({(long long)T * K}, i32);
+  hipLaunchKernelGGL(moe_route_kernel, dim3((unsigned)T), dim3(64), 0, stream,
+                     logits.data_ptr<float>(), r.topi.data_ptr<int>(),
+                     r.topw.data_ptr<float>(), E, K);
+  hipLaunchKernelGGL(moe_group_kernel, dim3(1), dim3(kGroupThreads), 0, stream,
+                     r.topi.data_ptr<int>(), r.offsets.data_ptr<int>(),
+                     r.pairs.data_ptr<int>(), T * K, E);
+  return r;
+}
+
+}  // namespace
+
+// router_logits fp32 [T, E] -> (topi int32 [T, K], topw fp32 [T, K],
+// offsets int32 [E + 1], pairs int32 [T * K])
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> moe_route(
+    torch::Tensor router_logits, long top_k) {
+  check_router(router_logits, top_k);
+  const long long T = router_logits.size(0), E = router_logits.size(1);
+  if (T == 0) {
+    const auto i32 = router_logits.options().dtype(torch::kInt32);
+    return {torch::empty({0, top_k}, i32), torch::empty({0, top_k}, router_logits.options()),
+            torch::zeros({E + 1}, i32), torch::empty({0}, i32)};
+  }
+  Routing r = route(router_logits, (int)top_k, hypha_stream());
+  return {r.topi, r.topw, r.offsets, r.pairs};
+}
+
+// x bf16 [T, h], router_logits fp32 [T, E], w_gate/w_up bf16 [E, f, h],
+// w_down bf16 [E, h, f] -> out bf16 [T, h]
+torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor router_logits, torch::Tensor w_gate,
+                      torch::Tensor w_up, torch::Tensor w_down, long top_k) {
+  check_router(router_logits, top_k);
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.dtype() == torch::kBFloat16 &&
+                  x.is_contiguous(),
+              "moe_ffn: x must be contiguous bf16 [T, h] on the GPU");
+  const long long T = x.size(0), h = x.size(1), E = router_logits.size(1);
+  TORCH_CHECK(router_logits.size(0) == T, "moe_ffn: router_logits must be [T, E]");
+  TORCH_CHECK(w_gate.is_cuda() && w_gate.dim() == 3 && w_gate.dtype() == torch::kBFloat16 &&
+                  w_gate.is_contiguous() && w_gate.size(0) == E && w_gate.size(2) == h,
+              "moe_ffn: w_gate must be contiguous bf16 [E, f, h] on the GPU");
+  const long long f = w_gate.size(1);
+  TORCH_CHECK(w_up.is_cuda() && w_up.dtype() == torch::kBFloat16 && w_up.is_contiguous() &&
+                  w_up.sizes() == w_gate.sizes(),
+              "moe_ffn: w_up must match w_gate");
+  TORCH_CHECK(w_down.is_cuda() && w_down.dim() == 3 && w_down.dtype() == torch::kBFloat16 &&
+                  w_down.is_contiguous() && w_down.size(0) == E && w_down.size(1) == h &&
+                  w_down.size(2) == f,
+              "moe_ffn: w_down must be contiguous bf16 [E, h, f] on the GPU");
+  TORCH_CHECK(h >= 128 && h % 128 == 0 && f >= 128 && f % 128 == 0 && h < (1 << 24) &&
+                  f < (1 << 24),
+              "moe_ffn: h and f must be multiples of 128");
+  auto out = torch::empty({T, h}, x.options());
+  if (T == 0) return out;
+
+  const int K = (int)top_k;
+  const long long P = T * K;
+  hipStream_t stream = hypha_stream();
+  Routing r = route(router_logits, K, stream);
+
+  // Split the down projection's k over workgroups until top_k live experts
+  // alone give about two workgroups per CU; a function of the shapes only.
+  const int nc_down = (int)((f + KC - 1) / KC);
+  int cps = nc_down;
+  if (P <= 256) {
+    const long long live = (h / 64) * K;
+    int want = (int)std::min<long long>((512 + live - 1) / live, 8);
+    want = std::max(1, std::min(want, nc_down));
+    cps = (nc_down + want - 1) / want;
+  }
+  const int S = (nc_down + cps - 1) / cps;
+
+  auto hbuf = torch::empty({P, f}, x.options());
+  auto ybuf = torch::empty({(long long)S, P, h}, x.options().dtype(torch::kFloat32));
+  const int* offs = r.offsets.data_ptr<int>();
+  const int* pairs = r.pairs.data_ptr<int>();
+  const float* topw = r.topw.data_ptr<float>();
+  hipLaunchKernelGGL(moe_expert_kernel<false>, dim3((unsigned)(f / 32), (unsigned)E, 1),
+                     dim3(256), 0, stream, (const short*)x.data_ptr(),
+                     (const short*)w_gate.data_ptr(), (const short*)w_up.data_ptr(), offs,
+                     pairs, topw, hbuf.data_ptr(), (int)h, (int)f, K, (int)P,
+                     (int)((h + KC - 1) / KC));
+  hipLaunchKernelGGL(moe_expert_kernel<true>, dim3((unsigned)(h / 64), (unsigned)E, (unsigned)S),
+                     dim3(256), 0, stream, (const short*)hbuf.data_ptr(),
+                     (const short*)w_down.data_ptr(), (const short*)nullptr, offs, pairs, topw,
+                     ybuf.data_ptr(), (int)f, (int)h, K, (int)P, cps);
+  const long long n_vec = T * (h / 8);
+  hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((n_vec + 255) / 256)), dim3(256), 0,
+                     stream, ybuf.data_ptr<float>(), (short*)out.data_ptr(), n_vec, (int)h, K,
+                     S, P);
+  return out;
+}

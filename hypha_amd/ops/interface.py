@@ -27,6 +27,8 @@ The HIP extension ABI (hypha_amd._C):
   grad_norm_sq(flat_bf16) -> fp32 scalar
   sample_token(logits_bf16, u_f32, temp_f32[1], top_k_i32[1], top_p_f32[1]) -> int64 [B, 1]
   philox_uniform(seed_i64[1], step_i64[1], n) -> fp32 [n]
+  moe_ffn(x_bf16, router_logits_f32, w_gate, w_up, w_down, top_k) -> bf16 [T, h]
+  moe_route(router_logits_f32, top_k) -> (topi_i32, topw_f32, offsets_i32, pairs_i32)
 """
 
 from __future__ import annotations
@@ -604,6 +606,50 @@ def linear_skinny(x2d: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
             and weight.dtype == torch.bfloat16):
         return _c().skinny_gemm(x2d.contiguous(), weight)
     return x2d @ weight.t()
+
+
+# ---------------------------------------------------------------------------
+# Routed expert FFN (MoE inference)
+# ---------------------------------------------------------------------------
+
+
+def moe_ffn_native_shapes(h: int, f: int, n_experts: int, top_k: int) -> bool:
+    """The shapes ops/hip/moe_ffn.hip serves."""
+    return (h >= 128 and h % 128 == 0 and f >= 128 and f % 128 == 0
+            and n_experts <= 64 and 1 <= top_k <= min(n_experts, 8))
+
+
+@torch.no_grad()
+def moe_ffn(x: torch.Tensor, router_logits: torch.Tensor, w_gate: torch.Tensor,
+            w_up: torch.Tensor, w_down: torch.Tensor, top_k: int) -> torch.Tensor:
+    """Top-k routed SwiGLU expert FFN at inference (MoEMLP's semantics):
+    x bf16 [T, h], router_logits fp32 [T, E], w_gate/w_up bf16 [E, f, h],
+    w_down bf16 [E, h, f] -> bf16 [T, h]. fp32 softmax over the experts,
+    top-k (among equal logits the lower index wins), the k weights
+    renormalised to sum 1, out[t] = sum_k w[t,k] * down_e(silu(gate_e x[t]) *
+    up_e x[t]). On the GPU (ops/hip/moe_ffn.hip) routing and grouping happen
+    on the device: no host sync, launches sized by the shapes alone (safe to
+    capture in a graph), no float atomics (bit-reproducible). Native for
+    h % 128 == 0, f % 128 == 0, E <= 64, top_k <= min(E, 8); the reference
+    for every other shape and for the CPU. No autograd."""
+    if x.dim() != 2 or router_logits.dim() != 2 or router_logits.shape[0] != x.shape[0]:
+        raise ValueError("moe_ffn: x must be [T, h] and router_logits [T, E]")
+    t, h = x.shape
+    n_experts = router_logits.shape[1]
+    if w_gate.dim() != 3 or w_gate.shape[0] != n_experts or w_gate.shape[2] != h:
+        raise ValueError("moe_ffn: w_gate must be [E, f, h]")
+    f = w_gate.shape[1]
+    if w_up.shape != w_gate.shape or tuple(w_down.shape) != (n_experts, h, f):
+        raise ValueError("moe_ffn: w_up must be [E, f, h] and w_down [E, h, f]")
+    if (router_logits.dtype != torch.float32
+            or any(a.dtype != torch.bfloat16 for a in (x, w_gate, w_up, w_down))):
+        raise ValueError("moe_ffn: x and the weights must be bf16, router_logits fp32")
+    if not isinstance(top_k, int) or not 1 <= top_k <= n_experts:
+        raise ValueError(f"moe_ffn: top_k must be an int in [1, {n_experts}], got {top_k}")
+    if use_native(x) and moe_ffn_native_shapes(h, f, n_experts, top_k):
+        return _c().moe_ffn(x.contiguous(), router_logits.contiguous(), w_gate.contiguous(),
+                            w_up.contiguous(), w_down.contiguous(), top_k)
+    return reference.moe_ffn(x, router_logits, w_gate, w_up, w_down, top_k)
 
 
 # ---------------------------------------------------------------------------

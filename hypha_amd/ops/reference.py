@@ -147,6 +147,28 @@ def swiglu(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
     return (F.silu(gate.float()) * up.float()).to(gate.dtype)
 
 
+def moe_ffn(x: torch.Tensor, router_logits: torch.Tensor, w_gate: torch.Tensor,
+            w_up: torch.Tensor, w_down: torch.Tensor, top_k: int) -> torch.Tensor:
+    """Top-k routed SwiGLU expert FFN at inference: x [T, h], router_logits
+    [T, E], w_gate/w_up [E, f, h], w_down [E, h, f] -> [T, h]. fp32 softmax,
+    top-k with the lower index winning ties, weights renormalised to sum 1."""
+    logits = router_logits.float()
+    probs = torch.softmax(logits, dim=-1)
+    topi = torch.sort(logits, dim=-1, descending=True, stable=True).indices[:, :top_k]
+    topw = probs.gather(1, topi)
+    topw = topw / topw.sum(-1, keepdim=True)
+    out = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
+    for e in range(w_gate.shape[0]):
+        tok, slot = (topi == e).nonzero(as_tuple=True)
+        if tok.numel() == 0:
+            continue
+        xe = x[tok]
+        he = swiglu(xe @ w_gate[e].t(), xe @ w_up[e].t())
+        ye = (he @ w_down[e].t()).float() * topw[tok, slot].unsqueeze(1)
+        out.index_add_(0, tok, ye)
+    return out.to(x.dtype)
+
+
 # ---------------------------------------------------------------------------
 # Cross-entropy over vocab (fp32 logits path)
 # ---------------------------------------------------------------------------

@@ -68,8 +68,11 @@ def build_hip_extension():
     # either way; they get the option so that the shared tile code is the
     # same instructions wherever it runs (the probe stands for the kernels).
     # No wrong value from a packed instruction has been seen in this project.
+    # moe_ffn.hip is built the same way: its fp32 work is the epilogue of a
+    # weight-streaming kernel, where packed VALU would buy nothing.
     no_pk_f32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-    extra = {"attn_fwd.hip": no_pk_f32, "prefill.hip": no_pk_f32, "probe.hip": no_pk_f32}
+    extra = {"attn_fwd.hip": no_pk_f32, "prefill.hip": no_pk_f32, "probe.hip": no_pk_f32,
+             "moe_ffn.hip": no_pk_f32}
     procs = []
     for src in sources:
         obj = objdir / (src.stem + ".o")
