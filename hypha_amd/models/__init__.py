@@ -46,3 +46,4 @@ for _name in moe.PRESETS:
 from .llama import LlamaConfig, LlamaForCausalLM  # noqa: E402,F401
 from .gpt2 import GPT2Config, GPT2ForCausalLM  # noqa: E402,F401
 from .moe import MoEConfig, MoEForCausalLM  # noqa: E402,F401
+from .fp8_linear import Fp8Linear, quantize_linears_fp8_  # noqa: E402,F401

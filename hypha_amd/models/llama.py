@@ -410,7 +410,7 @@ def _generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
               eos_token_id: int | None = None, pad_token_id: int = 0,
               top_p: float = 1.0, sampler: str = "multinomial",
               kv_layout: str = "contiguous", kv_pages: int | None = None,
-              kv_free_order=None):
+              kv_free_order=None, weight_quant: str | None = None):
     """Autoregressive generation with a per-layer KV cache (inference parity:
     the reference serves inference through the same executor surface).
     prefill_chunk feeds the prompt in pieces of at most that many tokens
@@ -438,9 +438,18 @@ def _generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
     exactly what the batch needs; too few raise PagePoolExhausted) and
     kv_free_order the order pages are handed out in (default ascending). The
     call always runs the per-sequence route (full lengths without
-    prompt_lens) and returns what the contiguous call would."""
+    prompt_lens) and returns what the contiguous call would.
+
+    weight_quant="fp8" first turns the model's bias-free linears into
+    weight-only fp8 ones, in place and once (models/fp8_linear.py: half the
+    weight bytes per decoded token); it sits next to kv_quant and changes
+    nothing on a model that is already quantised."""
+    from .fp8_linear import check_weight_quant, quantize_linears_fp8_
     from .kv_cache import KVCache
 
+    check_weight_quant(weight_quant)
+    if weight_quant == "fp8":
+        quantize_linears_fp8_(self)
     check_sampler(sampler, temperature, top_p, seed)
     if prefill_chunk is not None and prefill_chunk < 1:
         raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")

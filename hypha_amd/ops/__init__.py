@@ -68,10 +68,13 @@ from .interface import (  # noqa: E402
     gelu,
     kv_append_paged,
     layernorm,
+    linear_fp8w,
+    linear_fp8w_native_shapes,
     linear_skinny,
     moe_ffn,
     moe_ffn_native_shapes,
     philox_uniform,
+    quantize_rows_e4m3,
     rmsnorm,
     sample_token,
     swiglu,
@@ -100,6 +103,9 @@ __all__ = [
     "fused_adamw",
     "fused_nesterov",
     "linear_skinny",
+    "linear_fp8w",
+    "linear_fp8w_native_shapes",
+    "quantize_rows_e4m3",
     "extract_delta",
     "sample_token",
     "philox_uniform",

@@ -169,6 +169,13 @@ def moe_ffn(x: torch.Tensor, router_logits: torch.Tensor, w_gate: torch.Tensor,
     return out.to(x.dtype)
 
 
+def linear_fp8w(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """Weight-only fp8 linear: x [..., K], w8 e4m3 [N, K], scale fp32 [N] ->
+    [..., N] in x's dtype. The codes are exact in bf16 and fp32, so the GEMM
+    runs on exact weights; the per-row scale is one fp32 multiply after it."""
+    return ((x @ w8.to(x.dtype).t()).float() * scale).to(x.dtype)
+
+
 # ---------------------------------------------------------------------------
 # Cross-entropy over vocab (fp32 logits path)
 # ---------------------------------------------------------------------------

@@ -43,6 +43,7 @@ from __future__ import annotations
 import torch
 
 from hypha_amd import ops
+from hypha_amd.models.fp8_linear import Fp8Linear
 from hypha_amd.models.kv_cache import KVCache
 from hypha_amd.models.llama import RaggedStep, check_prompt_lens, prefill_ragged
 from hypha_amd.models.paged_kv import PagedKVCache, PageTable, pages_for
@@ -127,20 +128,27 @@ class GraphedDecoder:
         GEMMs run 2-D through hipBLASLt (the hand-written skinny-M GEMV,
         ops/hip/skinny_gemm.hip, measured 0.4 TB/s vs the library's 1.8-5.9
         on these shapes — shuffle-reduction issue-bound; kept as an opt-in
-        negative result like grouped_gemm)."""
+        negative result like grouped_gemm). A weight-only fp8 linear
+        (models/fp8_linear.py) runs its own module instead: ops.linear_fp8w,
+        the kernel of ops/hip/linear_fp8w.hip at these batch sizes."""
         m = self.model
         cfg = m.cfg
         b = self.batch
-        lin = lambda t, wt: t @ wt.t()  # noqa: E731
+
+        def lin(t, mod):
+            if isinstance(mod, Fp8Linear):
+                return mod(t)
+            return t @ mod.weight.t()
+
         x = m.embed(self.tok)
         cos = m.rope_cos.index_select(0, self.pos)
         sin = m.rope_sin.index_select(0, self.pos)
         for blk, cache in zip(m.blocks, self.caches):
             n1 = blk.attn_norm(x)[:, 0]  # [b, h]
             a = blk.attn
-            q = lin(n1, a.wq.weight).view(b, 1, cfg.n_heads, cfg.head_dim)
-            k = lin(n1, a.wk.weight).view(b, 1, cfg.n_kv_heads, cfg.head_dim)
-            v = lin(n1, a.wv.weight).view(b, 1, cfg.n_kv_heads, cfg.head_dim)
+            q = lin(n1, a.wq).view(b, 1, cfg.n_heads, cfg.head_dim)
+            k = lin(n1, a.wk).view(b, 1, cfg.n_kv_heads, cfg.head_dim)
+            v = lin(n1, a.wv).view(b, 1, cfg.n_kv_heads, cfg.head_dim)
             q, k = ops.apply_rope_qk(q, k, cos, sin, layout="bshd")
             cache.append_at(k, v, self.pos)
             if self.kv_quant == "fp8":
@@ -150,16 +158,15 @@ class GraphedDecoder:
             else:
                 o = self._C.attn_decode_graph(q[:, 0].contiguous(), cache.k,
                                               cache.v, self.t32)
-            attn_out = lin(o.reshape(b, -1), a.wo.weight).view(b, 1, -1)
+            attn_out = lin(o.reshape(b, -1), a.wo).view(b, 1, -1)
             x, n2 = ops.add_rmsnorm(x, attn_out, blk.mlp_norm.weight,
                                     blk.mlp_norm.eps)
             n2f = n2[:, 0]
-            h = ops.swiglu(lin(n2f, blk.mlp.w_gate.weight),
-                           lin(n2f, blk.mlp.w_up.weight))
-            x = x + lin(h, blk.mlp.w_down.weight).view(b, 1, -1)
+            h = ops.swiglu(lin(n2f, blk.mlp.w_gate),
+                           lin(n2f, blk.mlp.w_up))
+            x = x + lin(h, blk.mlp.w_down).view(b, 1, -1)
         x = m.norm(x)
-        head_w = m.lm_head.weight if m.lm_head is not None else m.embed.weight
-        logits = lin(x[:, 0], head_w)
+        logits = lin(x[:, 0], m.lm_head if m.lm_head is not None else m.embed)
         nxt = self._pick(logits, sample)  # [b, 1]
         self.step.clamp_(max=self.max_new - 1)
         self.out.index_copy_(1, self.step, nxt)
@@ -175,8 +182,12 @@ class GraphedDecoder:
         set the next input token."""
         m = self.model
         x = m.norm(x)
-        head_w = m.lm_head.weight if m.lm_head is not None else m.embed.weight
-        nxt = self._pick(x[:, 0] @ head_w.t(), sample)  # [b, 1]
+        if isinstance(m.lm_head, Fp8Linear):
+            logits = m.lm_head(x[:, 0])
+        else:
+            head_w = m.lm_head.weight if m.lm_head is not None else m.embed.weight
+            logits = x[:, 0] @ head_w.t()
+        nxt = self._pick(logits, sample)  # [b, 1]
         live = self.alive[:, None]
         at = self.n_cache.clamp(max=self.t_alloc - 1)[:, None]
         self.tokens_r.scatter_(1, at, torch.where(live, nxt, self.tokens_r.gather(1, at)))

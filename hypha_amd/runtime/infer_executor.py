@@ -12,7 +12,7 @@ so the scheduler's FSM and lease machinery apply unchanged.
 Job config: {"model", "data": <fetch ref>, "results": <send ref>?,
              "max_new_tokens", "batch_size", "seq_len", "temperature",
              "top_k", "top_p"?, "sampler": "philox"?, "seed"?,
-             "num_batches", "kv_cache": "fp8"?,
+             "num_batches", "kv_cache": "fp8"?, "weight_quant": "fp8"?,
              "prefill_chunk": <int>?, "pad_token_id": <int>?,
              "eos_token_id": <int>?, "kv_layout": "paged"?, "kv_pages": <int>?}
 
@@ -24,6 +24,9 @@ ops.sample_token from Philox uniforms). Without "sampler", a job with a
 temperature samples with torch.multinomial on the eager path. "kv_cache": "fp8" halves KV memory;
 "prefill_chunk" feeds each prompt in pieces of at most that many tokens
 (activation memory bounded by the chunk; absent = one pass).
+"weight_quant": "fp8" quantises the bias-free linears once after load to
+weight-only e4m3 with per-row scales (models/fp8_linear.py), halving the
+weight bytes a decode step reads; any other value is an error.
 
 "pad_token_id" makes every batch RAGGED: prompts are right-padded rows, a
 prompt's length is its row without the trailing run of that id (at least one
@@ -58,6 +61,14 @@ def prompt_lengths(prompts: torch.Tensor, pad_token_id: int) -> torch.Tensor:
     return last.amax(dim=1).clamp(min=1)
 
 
+def weight_quant(cfg: dict):
+    """The job's "weight_quant": None or "fp8"; anything else raises."""
+    from hypha_amd.models.fp8_linear import check_weight_quant
+
+    check_weight_quant(cfg.get("weight_quant"))
+    return cfg.get("weight_quant")
+
+
 def main() -> int:
     p = argparse.ArgumentParser()
     p.add_argument("--socket", required=True)
@@ -73,6 +84,7 @@ def main() -> int:
 
     with open(args.job) as f:
         cfg = json.load(f)
+    wq = weight_quant(cfg)
 
     session = Session(args.socket)
     from hypha_amd.telemetry import get_tracer
@@ -95,8 +107,10 @@ def main() -> int:
         if buf.dtype in (torch.bfloat16, torch.float16):
             buf.data = buf.data.float()
     model.eval()
+    if wq == "fp8":
+        models.quantize_linears_fp8_(model)
 
-    batch_size = int(cfg.get("batch_size", 1))
+    batch_size =int(cfg.get("batch_size", 1))
     seq_len = int(cfg.get("seq_len", 64))
     max_new = int(cfg.get("max_new_tokens", 32))
     num_batches = int(cfg.get("num_batches", 1))

@@ -69,10 +69,11 @@ def build_hip_extension():
     # same instructions wherever it runs (the probe stands for the kernels).
     # No wrong value from a packed instruction has been seen in this project.
     # moe_ffn.hip is built the same way: its fp32 work is the epilogue of a
-    # weight-streaming kernel, where packed VALU would buy nothing.
+    # weight-streaming kernel, where packed VALU would buy nothing; so is
+    # linear_fp8w.hip, for the same reason.
     no_pk_f32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     extra = {"attn_fwd.hip": no_pk_f32, "prefill.hip": no_pk_f32, "probe.hip": no_pk_f32,
-             "moe_ffn.hip": no_pk_f32}
+             "moe_ffn.hip": no_pk_f32, "linear_fp8w.hip": no_pk_f32}
     procs = []
     for src in sources:
         obj = objdir / (src.stem + ".o")

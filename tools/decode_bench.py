@@ -39,6 +39,9 @@ def main():
                         "(top-p needs sampler='philox')")
     p.add_argument("--kv-fp8", action="store_true",
                    help="fp8 (e4m3 + per-row scales) KV cache")
+    p.add_argument("--w-fp8", action="store_true",
+                   help="weight-only fp8 linears (e4m3 + per-row scales, "
+                        "ops.linear_fp8w)")
     p.add_argument("--ragged", metavar="LO:HI", default=None,
                    help="right-padded batch: prompt lengths drawn uniformly "
                         "from [LO, HI] (fixed seed, HI <= --prefill), generated "
@@ -64,6 +67,8 @@ def main():
     for buf in model.buffers():  # rope tables must stay fp32 for the kernels
         if buf.dtype in (torch.bfloat16, torch.float16):
             buf.data = buf.data.float()
+    if args.w_fp8:
+        models.quantize_linears_fp8_(model)
     ids = torch.randint(0, model.cfg.vocab_size - 1, (args.batch, args.prefill),
                         device=dev)
 
@@ -103,7 +108,7 @@ def main():
 
         gen = functools.partial(model.generate, kv_quant=kvq)
 
-    tag = ""
+    tag = " w-fp8" if args.w_fp8 else ""
     if args.sample is not None:
         import functools
 
@@ -117,7 +122,7 @@ def main():
             if not args.graph:
                 kw["sampler"] = "philox"
         gen = functools.partial(gen, **kw)
-        tag = f" sample {args.sample}"
+        tag += f" sample {args.sample}"
     if args.ragged is not None:
         import functools
 
