@@ -1,7 +1,9 @@
 """Weight-only fp8 linears for serving: each weight row is stored as e4m3
 codes with one fp32 scale (ops.quantize_rows_e4m3), half the bytes of bf16,
 and applied by ops.linear_fp8w: the weight-streaming HIP kernel for
-decode-sized batches, dequantise + library for prefill. Inference only."""
+decode-sized batches, dequantise + library for prefill. The experts of the MoE
+family are quantised the same way by MoEMLP.quantize_experts_fp8_ and applied
+by ops.moe_ffn_fp8w. Inference only."""
 
 from __future__ import annotations
 
@@ -48,7 +50,13 @@ def quantize_linears_fp8_(model: nn.Module) -> nn.Module:
     ops/hip/linear_fp8w.hip serves by an Fp8Linear (in the Llama family: wq,
     wk, wv, wo, w_gate, w_up, w_down and an untied lm_head). A linear that
     shares its weight with an embedding (a tied head), one with a bias and one
-    of another shape stay as they are. Returns the model in eval mode."""
+    of another shape stay as they are. The experts of every MoEMLP whose
+    shapes ops.moe_ffn_fp8w serves are quantised the same way
+    (MoEMLP.quantize_experts_fp8_); its router is a linear like any other
+    (with 8 outputs it is of another shape and stays bf16). Returns the model
+    in eval mode."""
+    from .moe import MoEMLP
+
     tied = {id(m.weight) for m in model.modules() if isinstance(m, nn.Embedding)}
     for parent in list(model.modules()):
         for name, child in list(parent.named_children()):
@@ -56,6 +64,10 @@ def quantize_linears_fp8_(model: nn.Module) -> nn.Module:
                     and id(child.weight) not in tied
                     and ops.linear_fp8w_native_shapes(*child.weight.shape)):
                 setattr(parent, name, Fp8Linear.from_linear(child))
+        if isinstance(parent, MoEMLP) and ops.moe_ffn_native_shapes(
+                parent.cfg.hidden_size, parent.cfg.ffn_hidden, parent.cfg.n_experts,
+                parent.cfg.top_k):
+            parent.quantize_experts_fp8_()
     return model.eval()
 
 

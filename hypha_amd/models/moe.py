@@ -29,6 +29,11 @@ class MoEConfig(LlamaConfig):
     # inference with at most this many tokens takes ops.moe_ffn (0 = never);
     # the measured crossover at Mixtral widths, profiles/moe_ffn.md
     fused_ffn_max_tokens: int = 64
+    # the same limit for weight-only fp8 experts: ops.moe_ffn_fp8w against the
+    # per-expert ops.linear_fp8w loop, which dequantises whole experts above
+    # 128 rows. The largest measured count at which the fused path won every
+    # round (3.8 against 5.1 ms; it loses at 2048), profiles/moe_ffn_fp8w.md
+    fused_ffn_fp8_max_tokens: int = 1024
 
     def num_params(self) -> int:
         h, v, f = self.hidden_size, self.vocab_size, self.ffn_hidden
@@ -124,13 +129,64 @@ class MoEMLP(nn.Module):
             nn.init.normal_(w, std=cfg.init_std)
         self.ep = None  # (rank, size, group) after shard_experts_
 
+    # buffers of a module with weight-only fp8 experts: codes [E, f, h],
+    # [E, f, h], [E, h, f] and one fp32 scale per expert and weight row
+    _FP8_BUFFERS = ("w_gate8", "s_gate", "w_up8", "s_up", "w_down8", "s_down")
+
+    @property
+    def experts_fp8(self) -> bool:
+        return "w_gate8" in self._buffers
+
+    @torch.no_grad()
+    def quantize_experts_fp8_(self) -> "MoEMLP":
+        """Replace the three expert parameters by e4m3 codes and fp32 row
+        scales (ops.quantize_rows_e4m3): half the bytes of bf16, served by
+        ops.moe_ffn_fp8w at decode sizes and by ops.linear_fp8w per expert
+        above them. Inference only; a second call changes nothing. Returns
+        the module in eval mode."""
+        if self.ep is not None:
+            raise ValueError("quantize_experts_fp8_: expert-parallel experts are not supported")
+        if not self.experts_fp8:
+            for name in ("gate", "up", "down"):
+                w = getattr(self, "w_" + name).detach()
+                delattr(self, "w_" + name)
+                q = [ops.quantize_rows_e4m3(we) for we in w]  # an expert at a time: fp32 temps
+                del w
+                self.register_buffer(f"w_{name}8", torch.stack([c for c, _ in q]))
+                self.register_buffer(f"s_{name}", torch.stack([s for _, s in q]))
+        return self.eval()
+
+    def _apply(self, fn, recurse=True):
+        # .to(dtype) / .bfloat16() cast every floating buffer; the codes and
+        # their fp32 scales must only ever move, so they pass as integers
+        kinds = {n: self._buffers[n].dtype for n in self._FP8_BUFFERS if n in self._buffers}
+        for n, dt in kinds.items():
+            self._buffers[n] = self._buffers[n].view(
+                torch.uint8 if dt == torch.float8_e4m3fn else torch.int32)
+        try:
+            super()._apply(fn, recurse)
+        finally:
+            for n, dt in kinds.items():
+                self._buffers[n] = self._buffers[n].view(dt)
+        return self
+
     def forward(self, x):
         cfg = self.cfg
         b, s, h = x.shape
         xf = x.reshape(-1, h)  # [T, h]
         t = xf.shape[0]
         logits = self.router(xf).float()  # [T, E]
-        if self._use_fused_ffn(xf):
+        if self.experts_fp8:
+            if self.training or torch.is_grad_enabled():
+                raise RuntimeError("MoEMLP: fp8 experts serve inference only "
+                                   "(eval mode under torch.no_grad())")
+            if self._use_fused_ffn_fp8(xf):
+                # the same device-routed path on one byte per weight
+                out = ops.moe_ffn_fp8w(xf.contiguous(), logits, self.w_gate8, self.s_gate,
+                                       self.w_up8, self.s_up, self.w_down8, self.s_down,
+                                       cfg.top_k)
+                return out.reshape(b, s, h), xf.new_zeros(())
+        elif self._use_fused_ffn(xf):
             # inference at decode sizes: routing, grouping and the expert
             # GEMMs on the device (ops/hip/moe_ffn.hip), no host sync
             out = ops.moe_ffn(xf.contiguous(), logits, self.w_gate, self.w_up,
@@ -173,7 +229,7 @@ class MoEMLP(nn.Module):
         import os
 
         use_native_grouped = (
-            os.environ.get("HYPHA_NATIVE_GROUPED", "0") == "1"
+            os.environ.get("HYPHA_NATIVE_GROUPED", "0") == "1" and not self.experts_fp8
             and not torch.is_grad_enabled() and gathered.is_cuda
             and gathered.dtype == torch.bfloat16 and ops.has_native()
             and cfg.ffn_hidden % 128 == 0 and cfg.hidden_size % 128 == 0
@@ -213,8 +269,21 @@ class MoEMLP(nn.Module):
                                           cfg.n_experts, cfg.top_k)
         )
 
+    def _use_fused_ffn_fp8(self, xf: torch.Tensor) -> bool:
+        """_use_fused_ffn for fp8 experts (the caller has checked eval mode and
+        no_grad); HYPHA_NATIVE_GROUPED has no meaning for them."""
+        cfg = self.cfg
+        return (
+            self.ep is None and xf.shape[0] <= cfg.fused_ffn_fp8_max_tokens
+            and xf.dtype == torch.bfloat16 and ops.use_native(xf)
+            and ops.moe_ffn_native_shapes(cfg.hidden_size, cfg.ffn_hidden,
+                                          cfg.n_experts, cfg.top_k)
+        )
+
     def _expert_ffn(self, xs: torch.Tensor, counts: list[int]) -> torch.Tensor:
-        """Per-expert SwiGLU chains over expert-grouped rows (local shard)."""
+        """Per-expert SwiGLU chains over expert-grouped rows (local shard). On
+        fp8 experts every projection is an ops.linear_fp8w: its kernel up to
+        128 rows per expert, dequantise and the library beyond."""
         out_groups = []
         start = 0
         for e in range(len(counts)):
@@ -222,10 +291,16 @@ class MoEMLP(nn.Module):
             if n == 0:
                 continue
             xe = xs[start:start + n]
-            ge = xe @ self.w_gate[e].t()
-            ue = xe @ self.w_up[e].t()
-            he = ops.swiglu(ge, ue)
-            out_groups.append(he @ self.w_down[e].t())
+            if self.experts_fp8:
+                ge = ops.linear_fp8w(xe, self.w_gate8[e], self.s_gate[e])
+                ue = ops.linear_fp8w(xe, self.w_up8[e], self.s_up[e])
+                he = ops.swiglu(ge, ue)
+                out_groups.append(ops.linear_fp8w(he, self.w_down8[e], self.s_down[e]))
+            else:
+                ge = xe @ self.w_gate[e].t()
+                ue = xe @ self.w_up[e].t()
+                he = ops.swiglu(ge, ue)
+                out_groups.append(he @ self.w_down[e].t())
             start += n
         return torch.cat(out_groups, dim=0) if out_groups else xs[:0]
 
@@ -385,13 +460,21 @@ class MoEForCausalLM(nn.Module):
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
                  temperature: float = 0.0, top_k: int = 0,
                  seed: int | None = None,
-                 prefill_chunk: int | None = None) -> torch.Tensor:
+                 prefill_chunk: int | None = None,
+                 weight_quant: str | None = None) -> torch.Tensor:
         """KV-cache decoding (prefill, then one token per step via the
         flash-decoding kernel; same sampling surface as the Llama family so
         inference jobs can run any registry model). prefill_chunk feeds the
-        prompt in pieces of at most that many tokens; None = one pass."""
+        prompt in pieces of at most that many tokens; None = one pass.
+        weight_quant="fp8" first turns the bias-free linears and the experts
+        into weight-only fp8 ones, in place and once (models/fp8_linear.py);
+        it changes nothing on a model that is already quantised."""
+        from .fp8_linear import check_weight_quant, quantize_linears_fp8_
         from .kv_cache import KVCache
 
+        check_weight_quant(weight_quant)
+        if weight_quant == "fp8":
+            quantize_linears_fp8_(self)
         if prefill_chunk is not None and prefill_chunk < 1:
             raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
         self.eval()

@@ -72,6 +72,7 @@ from .interface import (  # noqa: E402
     linear_fp8w_native_shapes,
     linear_skinny,
     moe_ffn,
+    moe_ffn_fp8w,
     moe_ffn_native_shapes,
     philox_uniform,
     quantize_rows_e4m3,
@@ -110,5 +111,6 @@ __all__ = [
     "sample_token",
     "philox_uniform",
     "moe_ffn",
+    "moe_ffn_fp8w",
     "moe_ffn_native_shapes",
 ]

@@ -159,6 +159,9 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> moe_route
     torch::Tensor router_logits, long top_k);
 torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor router_logits, torch::Tensor w_gate,
                       torch::Tensor w_up, torch::Tensor w_down, long top_k);
+torch::Tensor moe_ffn_fp8w(torch::Tensor x, torch::Tensor router_logits, torch::Tensor w_gate8,
+                           torch::Tensor s_gate, torch::Tensor w_up8, torch::Tensor s_up,
+                           torch::Tensor w_down8, torch::Tensor s_down, long top_k);
 // linear_fp8w.hip (weight-only e4m3 linear for decode-sized batches)
 torch::Tensor linear_fp8w(torch::Tensor x, torch::Tensor w8, torch::Tensor scale);
 
@@ -225,5 +228,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("philox_uniform", &philox_uniform);
   m.def("moe_route", &moe_route);
   m.def("moe_ffn", &moe_ffn);
+  m.def("moe_ffn_fp8w", &moe_ffn_fp8w);
   m.def("linear_fp8w", &linear_fp8w);
 }

@@ -50,26 +50,6 @@ constexpr int KC = 4 * KW;     // k per LDS chunk
 constexpr int PITCH = KC + 8;  // LDS row pitch (1040 B = 65 x 16 B: conflict-free b128 reads)
 constexpr int XL = KC * NT / (256 * 8);  // 16-byte activation loads per thread per chunk
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
-// four e4m3 codes -> four bf16 (two dwords), exactly
-__device__ __forceinline__ u32x2 e4m3x4_to_bf16x4(unsigned int d) {
-  const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)d, false);
-  const f32x2 b = __builtin_amdgcn_cvt_pk_f32_fp8((int)d, true);
-  u32x2 o;
-  o[0] = __builtin_amdgcn_perm(__float_as_uint(a[1]), __float_as_uint(a[0]), 0x07060302u);
-  o[1] = __builtin_amdgcn_perm(__float_as_uint(b[1]), __float_as_uint(b[0]), 0x07060302u);
-  return o;
-}
-
-// eight e4m3 codes -> one bf16 MFMA operand
-__device__ __forceinline__ s16x8 e4m3x8_to_bf16x8(unsigned int d0, unsigned int d1) {
-  const u32x2 lo = e4m3x4_to_bf16x4(d0), hi = e4m3x4_to_bf16x4(d1);
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(s16x8, v);
-}
-
 // SPLIT = false: outp = out bf16 [M, N], scaled. gridDim.y == 1.
 // SPLIT = true : outp = part fp32 [gridDim.y, M, N], unscaled.
 template <bool SPLIT>

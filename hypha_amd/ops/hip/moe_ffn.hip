@@ -40,9 +40,63 @@
 // An expert with more than 32 pairs loops over token tiles and re-reads its
 // weight tile from L2; columns past the count are zero in LDS and never
 // stored.
+//
+// Weight-only fp8 experts (moe_ffn_fp8w): the same five launches with
+// moe_expert_fp8w_kernel<DOWN> in place of moe_expert_kernel. The weights are
+// e4m3 codes, one byte each, with one fp32 scale per expert and row. Every
+// finite e4m3 value is a bf16 value, so a code becomes its bf16 in registers
+// (v_cvt_pk_f32_fp8 gives two exact fp32, one v_perm_b32 keeps their high
+// halves) and the GEMMs are the same bf16 MFMAs on exact operands; no
+// dequantised copy exists in global memory or LDS. The scale is applied once
+// per output element, in fp32, in the epilogue: g = acc_g * s_gate[e, row],
+// u = acc_u * s_up[e, row], v = silu(g) * u; ybuf = acc * s_down[e, row] *
+// w[pair], which is linear in acc, so split-K stays valid.
+// hbuf [P, 2, f] holds v as two bf16 rows, hi = bf16(v) and lo = bf16(v - hi)
+// (v - hi is exact in fp32). One bf16 rounding of v, 2^-9 relative, is an
+// absolute error of the output that grows with the norm of the W_down row:
+// with row scales 16x apart it passes 3e-2 on outputs near 0 at Mixtral's
+// f. The down stage therefore takes a pair's hi and lo rows as two neighbouring
+// N columns (16 pairs per 32-column tile), runs the same MFMAs per tile and
+// adds the two accumulators in the epilogue by one lane swap: the
+// intermediate has 16 bits of significand, LDS and registers are unchanged,
+// and only an expert with more than 16 pairs pays, by a second pass over its
+// weight tile (T = 64 and up, profiles/moe_ffn_fp8w.md).
+// The kernel keeps its parent's structure (early exit, two 32-row tiles per
+// workgroup, tokens on N, waves split by k, partials met in LDS in wave
+// order) with the k geometry of 1-byte weights, which is linear_fp8w.hip's:
+//   chunk   512 k, so that each of the four waves still owns one whole
+//           128-byte line of each of its 64 code rows: wave w takes k in
+//           [128 w, 128 w + 128), four 16-byte loads per lane per tile; lane
+//           (m, hi) of load j holds k = 32 j + 16 hi .. + 16, bytes 0-7 the A
+//           operand of MFMA step 2 j, bytes 8-15 that of step 2 j + 1, and B
+//           is read from LDS at the same k. 8 KiB of codes in flight per wave.
+//   gather  a wave stages whole rows: lane l holds k = 8 l .. + 8 of slots
+//           w + 4 i, i < 8, so the slot's source row (pairs[off + s] / top_k
+//           for gate/up; row 2 pairs[off + s / 2] + s % 2 of hbuf for down)
+//           is wave-uniform. A slot
+//           past the count is zeroed in both buffers once per token tile and
+//           neither loaded nor stored afterwards.
+//   tail    h and f are multiples of 128, not of 512: in the last chunk the
+//           lanes whose k lies past the end stage zeros, and the waves whose
+//           line starts past the end load no codes and issue no MFMA.
+//   LDS     pitch 520 shorts (1040 B = 65 x 16 B: conflict-free b128 reads),
+//           2 x 32 x 520 x 2 B = 66560 B a workgroup. Two workgroups fit the
+//           CU's 160 KiB, three do not, so the target is 2 waves/SIMD
+//           (__launch_bounds__(256, 2)): 206 / 204 VGPR (gate/up / down), 0
+//           AGPR, 0 scratch. The parent's third wave would need chunks of 384
+//           k at most, which four whole-line waves cannot make; the measured
+//           rates (profiles/moe_ffn_fp8w.md: 3.9 and 4.5 TB/s of codes at
+//           T = 1) are those of the bf16 kernel at 3 waves/SIMD.
+// The down projection's split is the same rule on chunks of 512: at Mixtral
+// widths and T = 1 (h 4096, f 14336, top-2) f has 28 chunks, the 2 x 64 live
+// row tiles ask for 4 splits of 7 chunks, so 512 workgroups are live in the
+// down stage (one full residency of 256 CUs x 2) and 2 x 448 = 896 in
+// gate/up, out of 2048 and 3584 launched.
 
 #include <torch/extension.h>
 
+#include <algorithm>
+#include <cstdint>
 #include <tuple>
 
 #include "hip_common.h"
@@ -303,6 +357,204 @@ __global__ __launch_bounds__(256, 3) void moe_expert_kernel(
   }
 }
 
+// ---- expert GEMMs on weight-only fp8 experts -----------------------------------
+
+constexpr int KW8 = 128;         // k per wave per chunk: one 128-byte line of a code row
+constexpr int KC8 = 4 * KW8;     // k per LDS chunk
+constexpr int PITCH8 = KC8 + 8;  // LDS row pitch (1040 B = 65 x 16 B: conflict-free b128 reads)
+constexpr int XL8 = KC8 * NT / (256 * 8);  // 16-byte activation loads per thread per chunk
+
+// moe_expert_kernel on e4m3 codes with one fp32 scale per expert and row.
+// DOWN = false: act = x [T, Kd], wa/wb = W8_gate/W8_up [E, R, Kd], sa/sb =
+//               s_gate/s_up [E, R], 32-row tiles, out = hbuf bf16 [P, 2, R].
+// DOWN = true : act = hbuf [P, 2, Kd], wa = W8_down [E, R, Kd], sa = s_down [E, R],
+//               64-row tiles, out = ybuf fp32 [gridDim.z, P, R]; split z takes
+//               the chunks [z * cps, (z + 1) * cps).
+template <bool DOWN>
+__global__ __launch_bounds__(256, 2) void moe_expert_fp8w_kernel(
+    const short* __restrict__ act, const unsigned char* __restrict__ wa,
+    const unsigned char* __restrict__ wb, const float* __restrict__ sa,
+    const float* __restrict__ sb, const int* __restrict__ offsets,
+    const int* __restrict__ pairs, const float* __restrict__ topw,
+    void* __restrict__ outp, int Kd, int R, int top_k, int P, int cps) {
+  const int e = blockIdx.y;
+  const int off = offsets[e];
+  const int cnt = offsets[e + 1] - off;
+  if (cnt == 0) return;  // nobody chose this expert: no weight is read
+  // N slots of this expert: a pair in gate/up; in down a pair's hi row of
+  // hbuf (slot 2 i) and its lo row (slot 2 i + 1), 16 pairs per token tile
+  const int ns = DOWN ? 2 * cnt : cnt;
+
+  __shared__ __attribute__((aligned(16))) short xs[2 * NT * PITCH8];
+  float* red = reinterpret_cast<float*>(xs);  // [4 waves][2 tiles][16][64] after the k loop
+  static_assert(4 * 2 * 16 * 64 * sizeof(float) <= sizeof(short) * 2 * NT * PITCH8,
+                "reduction image must fit the staging buffers");
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, w = tid >> 6;
+  const int ln = lane & 31, hi = lane >> 5;
+  const int rows0 = blockIdx.x * (DOWN ? 64 : 32);
+  const long long row = (long long)e * R + rows0 + ln;
+  const unsigned char* a0 = wa + row * Kd + w * KW8 + 16 * hi;
+  const unsigned char* a1 = DOWN ? a0 + 32ll * Kd : wb + row * Kd + w * KW8 + 16 * hi;
+  const int nc = (Kd + KC8 - 1) / KC8;
+  const int c0 = blockIdx.z * cps;
+  const int c1 = min(nc, c0 + cps);
+  const int xk = lane * 8;  // staging: k inside the chunk; wave w stages slots w + 4 i
+
+  for (int t0 = 0; t0 < ns; t0 += NT) {
+    // activation row of each slot this wave stages (wave-uniform); a slot past
+    // the count is zeroed in both buffers here and never loaded or stored again
+    int rowi[XL8];
+#pragma unroll
+    for (int i = 0; i < XL8; ++i) {
+      const int s = t0 + w + 4 * i;
+      rowi[i] = -1;
+      if (s < ns) {
+        rowi[i] = DOWN ? 2 * pairs[off + (s >> 1)] + (s & 1) : pairs[off + s] / top_k;
+      } else {
+        *reinterpret_cast<s16x8*>(xs + (w + 4 * i) * PITCH8 + xk) = s16x8{};
+        *reinterpret_cast<s16x8*>(xs + (NT + w + 4 * i) * PITCH8 + xk) = s16x8{};
+      }
+    }
+    // a lane whose k lies past Kd (the last chunk of a Kd that is no multiple
+    // of KC8) stages zeros; the waves that own that k skip their MFMAs anyway
+    auto load_x = [&](int c, s16x8(&xr)[XL8]) {
+      const int k = c * KC8 + xk;
+#pragma unroll
+      for (int i = 0; i < XL8; ++i) {
+        xr[i] = s16x8{};
+        if (rowi[i] >= 0 && k < Kd)
+          xr[i] = *reinterpret_cast<const s16x8*>(act + (long long)rowi[i] * Kd + k);
+      }
+    };
+    auto store_x = [&](int buf, const s16x8(&xr)[XL8]) {
+#pragma unroll
+      for (int i = 0; i < XL8; ++i)
+        if (rowi[i] >= 0)
+          *reinterpret_cast<s16x8*>(xs + (buf * NT + w + 4 * i) * PITCH8 + xk) = xr[i];
+    };
+    // this wave's 128 k of chunk c: one 128-byte line of each code row; lane
+    // (m, hi) of load j holds the 16 codes k = 32 j + 16 hi .. + 16
+    auto load_w = [&](int c, u32x4(&wr)[2][4]) {
+      if (c * KC8 + w * KW8 < Kd) {  // Kd % 128 == 0, so a started line is whole
+        const long long kb = (long long)c * KC8;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          wr[0][j] = *reinterpret_cast<const u32x4*>(a0 + kb + 32 * j);
+          wr[1][j] = *reinterpret_cast<const u32x4*>(a1 + kb + 32 * j);
+        }
+      }
+    };
+
+    f32x16 acc0 = {}, acc1 = {};
+    u32x4 wcur[2][4] = {}, wnxt[2][4] = {};
+    s16x8 xr[XL8];
+    load_x(c0, xr);
+    load_w(c0, wcur);
+    store_x(0, xr);
+    __syncthreads();
+    for (int c = c0; c < c1; ++c) {
+      const int buf = (c - c0) & 1;
+      const bool more = c + 1 < c1;
+      if (more) {
+        load_x(c + 1, xr);
+        load_w(c + 1, wnxt);
+      }
+      if (c * KC8 + w * KW8 < Kd) {
+        // bytes 0-7 of load j are the A operand of MFMA step 2 j, bytes 8-15
+        // that of step 2 j + 1; B is read at the same k, so nothing is shuffled
+        const short* bp = xs + (buf * NT + ln) * PITCH8 + w * KW8 + 16 * hi;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const s16x8 b0 = *reinterpret_cast<const s16x8*>(bp + 32 * j);
+          const s16x8 b1 = *reinterpret_cast<const s16x8*>(bp + 32 * j + 8);
+          acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              e4m3x8_to_bf16x8(wcur[0][j][0], wcur[0][j][1]), b0, acc0, 0, 0, 0);
+          acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              e4m3x8_to_bf16x8(wcur[0][j][2], wcur[0][j][3]), b1, acc0, 0, 0, 0);
+          acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              e4m3x8_to_bf16x8(wcur[1][j][0], wcur[1][j][1]), b0, acc1, 0, 0, 0);
+          acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              e4m3x8_to_bf16x8(wcur[1][j][2], wcur[1][j][3]), b1, acc1, 0, 0, 0);
+        }
+      }
+      if (more) store_x(buf ^ 1, xr);
+      __syncthreads();
+      if (more) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          wcur[0][j] = wnxt[0][j];
+          wcur[1][j] = wnxt[1][j];
+        }
+      }
+    }
+
+    // the four waves' partial sums meet in LDS and are added in wave order
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      red[((w * 2 + 0) * 16 + r) * 64 + lane] = acc0[r];
+      red[((w * 2 + 1) * 16 + r) * 64 + lane] = acc1[r];
+    }
+    __syncthreads();
+    // thread (n, q): token n, tile rows 8 (q >> 1) + 4 (q & 1) .. + 4, which
+    // are registers 4 (q >> 1) .. + 4 of MFMA lane 32 (q & 1) + n
+    const int n = tid & 31, q = tid >> 5;
+    f32x4 s0, s1;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = 4 * (q >> 1) + i, src = 32 * (q & 1) + n;
+      s0[i] = 0.f;
+      s1[i] = 0.f;
+#pragma unroll
+      for (int ww = 0; ww < 4; ++ww) {
+        s0[i] += red[((ww * 2 + 0) * 16 + r) * 64 + src];
+        s1[i] += red[((ww * 2 + 1) * 16 + r) * 64 + src];
+      }
+    }
+    if (DOWN) {  // hi + lo: a pair's two columns sit on neighbouring lanes
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        s0[i] += __shfl_xor(s0[i], 1, 64);
+        s1[i] += __shfl_xor(s1[i], 1, 64);
+      }
+    }
+    if (t0 + n < ns && !(DOWN && (n & 1))) {
+      const int p = pairs[off + (DOWN ? (t0 + n) >> 1 : t0 + n)];
+      const int m = rows0 + 8 * (q >> 1) + 4 * (q & 1);
+      // the only place a scale is used: once per output element, in fp32
+      const long long srow = (long long)e * R + m;
+      const f32x4 sc0 = *reinterpret_cast<const f32x4*>(sa + srow);
+      const f32x4 sc1 = *reinterpret_cast<const f32x4*>(DOWN ? sa + srow + 32 : sb + srow);
+      if (!DOWN) {
+        s16x4 o, lo;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float g = s0[i] * sc0[i], u = s1[i] * sc1[i];
+          const float v = g / (1.f + __expf(-g)) * u;
+          o[i] = f2bf(v);
+          lo[i] = f2bf(v - bf2f(o[i]));  // what the rounding dropped, exact in fp32
+        }
+        short* hp = static_cast<short*>(outp) + 2ll * p * R + m;
+        *reinterpret_cast<s16x4*>(hp) = o;
+        *reinterpret_cast<s16x4*>(hp + R) = lo;
+      } else {
+        const float wt = topw[p];
+        float* y = static_cast<float*>(outp) + ((long long)blockIdx.z * P + p) * R + m;
+        f32x4 y0, y1;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          y0[i] = s0[i] * sc0[i] * wt;
+          y1[i] = s1[i] * sc1[i] * wt;
+        }
+        *reinterpret_cast<f32x4*>(y) = y0;
+        *reinterpret_cast<f32x4*>(y + 32) = y1;
+      }
+    }
+    __syncthreads();  // red aliases the next token tile's staging buffers
+  }
+}
+
 // out[t, c .. c + 8] = bf16(sum_k (sum_s ybuf[s, t K + k, c .. c + 8]))
 __global__ __launch_bounds__(256) void moe_combine_kernel(
     const float* __restrict__ ybuf, short* __restrict__ out, long long n_vec, int h,
@@ -370,6 +622,17 @@ Routing route(const torch::Tensor& logits, int K, hipStream_t stream) {
   return r;
 }
 
+// Chunks per split of the down projection: k is split over workgroups until
+// top_k live experts alone give about two workgroups per CU (512 on 256 CUs),
+// at most 8 ways; a function of the shapes only. nc = number of k chunks.
+int down_chunks_per_split(int nc, long long h, int K, long long P) {
+  if (P > 256) return nc;
+  const long long live = (h / 64) * K;
+  int want = (int)std::min<long long>((512 + live - 1) / live, 8);
+  want = std::max(1, std::min(want, nc));
+  return (nc + want - 1) / want;
+}
+
 }  // namespace
 
 // router_logits fp32 [T, E] -> (topi int32 [T, K], topw fp32 [T, K],
@@ -419,16 +682,8 @@ torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor router_logits, torch::Tenso
   hipStream_t stream = hypha_stream();
   Routing r = route(router_logits, K, stream);
 
-  // Split the down projection's k over workgroups until top_k live experts
-  // alone give about two workgroups per CU; a function of the shapes only.
   const int nc_down = (int)((f + KC - 1) / KC);
-  int cps = nc_down;
-  if (P <= 256) {
-    const long long live = (h / 64) * K;
-    int want = (int)std::min<long long>((512 + live - 1) / live, 8);
-    want = std::max(1, std::min(want, nc_down));
-    cps = (nc_down + want - 1) / want;
-  }
+  const int cps = down_chunks_per_split(nc_down, h, K, P);
   const int S = (nc_down + cps - 1) / cps;
 
   auto hbuf = torch::empty({P, f}, x.options());
@@ -445,6 +700,75 @@ torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor router_logits, torch::Tenso
                      dim3(256), 0, stream, (const short*)hbuf.data_ptr(),
                      (const short*)w_down.data_ptr(), (const short*)nullptr, offs, pairs, topw,
                      ybuf.data_ptr(), (int)f, (int)h, K, (int)P, cps);
+  const long long n_vec = T * (h / 8);
+  hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((n_vec + 255) / 256)), dim3(256), 0,
+                     stream, ybuf.data_ptr<float>(), (short*)out.data_ptr(), n_vec, (int)h, K,
+                     S, P);
+  return out;
+}
+
+// x bf16 [T, h], router_logits fp32 [T, E], w_gate8/w_up8 e4m3 [E, f, h] with
+// s_gate/s_up fp32 [E, f], w_down8 e4m3 [E, h, f] with s_down fp32 [E, h]
+// -> out bf16 [T, h]
+torch::Tensor moe_ffn_fp8w(torch::Tensor x, torch::Tensor router_logits, torch::Tensor w_gate8,
+                           torch::Tensor s_gate, torch::Tensor w_up8, torch::Tensor s_up,
+                           torch::Tensor w_down8, torch::Tensor s_down, long top_k) {
+  check_router(router_logits, top_k);
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.dtype() == torch::kBFloat16 &&
+                  x.is_contiguous(),
+              "moe_ffn_fp8w: x must be contiguous bf16 [T, h] on the GPU");
+  const long long T = x.size(0), h = x.size(1), E = router_logits.size(1);
+  TORCH_CHECK(router_logits.size(0) == T, "moe_ffn_fp8w: router_logits must be [T, E]");
+  auto codes = [&](const torch::Tensor& w, long long rows, long long cols) {
+    return w.is_cuda() && w.dim() == 3 && w.dtype() == torch::kFloat8_e4m3fn &&
+           w.is_contiguous() && w.size(0) == E && w.size(1) == rows && w.size(2) == cols;
+  };
+  auto scales = [&](const torch::Tensor& s, long long rows) {
+    return s.is_cuda() && s.dim() == 2 && s.dtype() == torch::kFloat32 && s.is_contiguous() &&
+           s.size(0) == E && s.size(1) == rows;
+  };
+  TORCH_CHECK(w_gate8.dim() == 3, "moe_ffn_fp8w: w_gate8 must be [E, f, h]");
+  const long long f = w_gate8.size(1);
+  TORCH_CHECK(codes(w_gate8, f, h) && codes(w_up8, f, h) && codes(w_down8, h, f),
+              "moe_ffn_fp8w: the codes must be contiguous e4m3 [E, f, h], [E, f, h] and "
+              "[E, h, f] on the GPU");
+  TORCH_CHECK(scales(s_gate, f) && scales(s_up, f) && scales(s_down, h),
+              "moe_ffn_fp8w: the scales must be contiguous fp32 [E, f], [E, f] and [E, h] on "
+              "the GPU");
+  TORCH_CHECK(h >= 128 && h % 128 == 0 && f >= 128 && f % 128 == 0 && h < (1 << 24) &&
+                  f < (1 << 24),
+              "moe_ffn_fp8w: h and f must be multiples of 128");
+  for (const torch::Tensor* t : {&x, &w_gate8, &w_up8, &w_down8, &s_gate, &s_up, &s_down})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "moe_ffn_fp8w: operands must be 16-byte aligned");
+  auto out = torch::empty({T, h}, x.options());
+  if (T == 0) return out;
+
+  const int K = (int)top_k;
+  const long long P = T * K;
+  hipStream_t stream = hypha_stream();
+  Routing r = route(router_logits, K, stream);
+
+  const int nc_down = (int)((f + KC8 - 1) / KC8);
+  const int cps = down_chunks_per_split(nc_down, h, K, P);
+  const int S = (nc_down + cps - 1) / cps;
+
+  auto hbuf = torch::empty({P, 2, f}, x.options());  // hi and lo row of each pair
+  auto ybuf = torch::empty({(long long)S, P, h}, x.options().dtype(torch::kFloat32));
+  const int* offs = r.offsets.data_ptr<int>();
+  const int* pairs = r.pairs.data_ptr<int>();
+  const float* topw = r.topw.data_ptr<float>();
+  using u8 = unsigned char;
+  hipLaunchKernelGGL(moe_expert_fp8w_kernel<false>, dim3((unsigned)(f / 32), (unsigned)E, 1),
+                     dim3(256), 0, stream, (const short*)x.data_ptr(),
+                     (const u8*)w_gate8.data_ptr(), (const u8*)w_up8.data_ptr(),
+                     s_gate.data_ptr<float>(), s_up.data_ptr<float>(), offs, pairs, topw,
+                     hbuf.data_ptr(), (int)h, (int)f, K, (int)P, (int)((h + KC8 - 1) / KC8));
+  hipLaunchKernelGGL(moe_expert_fp8w_kernel<true>,
+                     dim3((unsigned)(h / 64), (unsigned)E, (unsigned)S), dim3(256), 0, stream,
+                     (const short*)hbuf.data_ptr(), (const u8*)w_down8.data_ptr(),
+                     (const u8*)nullptr, s_down.data_ptr<float>(), (const float*)nullptr, offs,
+                     pairs, topw, ybuf.data_ptr(), (int)f, (int)h, K, (int)P, cps);
   const long long n_vec = T * (h / 8);
   hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((n_vec + 255) / 256)), dim3(256), 0,
                      stream, ybuf.data_ptr<float>(), (short*)out.data_ptr(), n_vec, (int)h, K,

@@ -28,6 +28,8 @@ The HIP extension ABI (hypha_amd._C):
   sample_token(logits_bf16, u_f32, temp_f32[1], top_k_i32[1], top_p_f32[1]) -> int64 [B, 1]
   philox_uniform(seed_i64[1], step_i64[1], n) -> fp32 [n]
   moe_ffn(x_bf16, router_logits_f32, w_gate, w_up, w_down, top_k) -> bf16 [T, h]
+  moe_ffn_fp8w(x_bf16, router_logits_f32, w_gate8, s_gate, w_up8, s_up, w_down8, s_down,
+               top_k) -> bf16 [T, h]
   moe_route(router_logits_f32, top_k) -> (topi_i32, topw_f32, offsets_i32, pairs_i32)
   linear_fp8w(x_bf16 [M, K], w8_e4m3 [N, K], scale_f32 [N]) -> bf16 [M, N]
 """
@@ -699,6 +701,51 @@ def moe_ffn(x: torch.Tensor, router_logits: torch.Tensor, w_gate: torch.Tensor,
         return _c().moe_ffn(x.contiguous(), router_logits.contiguous(), w_gate.contiguous(),
                             w_up.contiguous(), w_down.contiguous(), top_k)
     return reference.moe_ffn(x, router_logits, w_gate, w_up, w_down, top_k)
+
+
+@torch.no_grad()
+def moe_ffn_fp8w(x: torch.Tensor, router_logits: torch.Tensor, w_gate8: torch.Tensor,
+                 s_gate: torch.Tensor, w_up8: torch.Tensor, s_up: torch.Tensor,
+                 w_down8: torch.Tensor, s_down: torch.Tensor, top_k: int) -> torch.Tensor:
+    """ops.moe_ffn on weight-only fp8 experts: x bf16 [T, h], router_logits
+    fp32 [T, E], w_gate8/w_up8 float8_e4m3fn [E, f, h] with s_gate/s_up fp32
+    [E, f], w_down8 float8_e4m3fn [E, h, f] with s_down fp32 [E, h] -> bf16
+    [T, h]; W = codes * scale[..., None], as ops.quantize_rows_e4m3(W)
+    produces them for a 3-D weight. Routing as ops.moe_ffn; each projection is
+    (codes . v) * scale: every e4m3 value is a bf16 value, so the GEMMs run on
+    exact operands with fp32 accumulation and the scale is one fp32 multiply
+    per output element. On the GPU (moe_expert_fp8w_kernel in ops/hip/
+    moe_ffn.hip) only the chosen experts' codes are read, one byte per weight:
+    no host sync, launches sized by the shapes alone (safe to capture in a
+    graph), no float atomics (bit-reproducible). Native for the shapes of
+    moe_ffn_native_shapes; reference.moe_ffn_fp8w for every other shape and
+    for the CPU. No autograd."""
+    if x.dim() != 2 or router_logits.dim() != 2 or router_logits.shape[0] != x.shape[0]:
+        raise ValueError("moe_ffn_fp8w: x must be [T, h] and router_logits [T, E]")
+    t, h = x.shape
+    n_experts = router_logits.shape[1]
+    if w_gate8.dim() != 3 or w_gate8.shape[0] != n_experts or w_gate8.shape[2] != h:
+        raise ValueError("moe_ffn_fp8w: w_gate8 must be [E, f, h]")
+    f = w_gate8.shape[1]
+    if w_up8.shape != w_gate8.shape or tuple(w_down8.shape) != (n_experts, h, f):
+        raise ValueError("moe_ffn_fp8w: w_up8 must be [E, f, h] and w_down8 [E, h, f]")
+    if (tuple(s_gate.shape) != (n_experts, f) or tuple(s_up.shape) != (n_experts, f)
+            or tuple(s_down.shape) != (n_experts, h)):
+        raise ValueError("moe_ffn_fp8w: s_gate and s_up must be [E, f] and s_down [E, h]")
+    if (x.dtype != torch.bfloat16 or router_logits.dtype != torch.float32
+            or any(a.dtype != torch.float8_e4m3fn for a in (w_gate8, w_up8, w_down8))
+            or any(a.dtype != torch.float32 for a in (s_gate, s_up, s_down))):
+        raise ValueError("moe_ffn_fp8w: x must be bf16, the codes float8_e4m3fn, the scales "
+                         "and router_logits fp32")
+    if not isinstance(top_k, int) or not 1 <= top_k <= n_experts:
+        raise ValueError(f"moe_ffn_fp8w: top_k must be an int in [1, {n_experts}], got {top_k}")
+    if use_native(x) and moe_ffn_native_shapes(h, f, n_experts, top_k):
+        return _c().moe_ffn_fp8w(x.contiguous(), router_logits.contiguous(),
+                                 w_gate8.contiguous(), s_gate.contiguous(),
+                                 w_up8.contiguous(), s_up.contiguous(),
+                                 w_down8.contiguous(), s_down.contiguous(), top_k)
+    return reference.moe_ffn_fp8w(x, router_logits, w_gate8, s_gate, w_up8, s_up, w_down8,
+                                  s_down, top_k)
 
 
 # ---------------------------------------------------------------------------

@@ -176,6 +176,29 @@ def linear_fp8w(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor) -> torch
     return ((x @ w8.to(x.dtype).t()).float() * scale).to(x.dtype)
 
 
+def moe_ffn_fp8w(x: torch.Tensor, router_logits: torch.Tensor, w_gate8: torch.Tensor,
+                 s_gate: torch.Tensor, w_up8: torch.Tensor, s_up: torch.Tensor,
+                 w_down8: torch.Tensor, s_down: torch.Tensor, top_k: int) -> torch.Tensor:
+    """moe_ffn on weight-only fp8 experts (codes [E, f, h], [E, f, h], [E, h, f]
+    with one fp32 scale per expert and row): the same routing, each projection
+    a linear_fp8w."""
+    logits = router_logits.float()
+    probs = torch.softmax(logits, dim=-1)
+    topi = torch.sort(logits, dim=-1, descending=True, stable=True).indices[:, :top_k]
+    topw = probs.gather(1, topi)
+    topw = topw / topw.sum(-1, keepdim=True)
+    out = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
+    for e in range(w_gate8.shape[0]):
+        tok, slot = (topi == e).nonzero(as_tuple=True)
+        if tok.numel() == 0:
+            continue
+        xe = x[tok]
+        he = swiglu(linear_fp8w(xe, w_gate8[e], s_gate[e]), linear_fp8w(xe, w_up8[e], s_up[e]))
+        ye = linear_fp8w(he, w_down8[e], s_down[e]).float() * topw[tok, slot].unsqueeze(1)
+        out.index_add_(0, tok, ye)
+    return out.to(x.dtype)
+
+
 # ---------------------------------------------------------------------------
 # Cross-entropy over vocab (fp32 logits path)
 # ---------------------------------------------------------------------------

@@ -4,13 +4,20 @@ token count. Device events around `iters` forwards over 8 rotating inputs
 (so the routing varies), the two paths alternated `rounds` times; the median
 round and the spread are printed, one JSON line per T.
 
-  python tools/moe_ffn_bench.py [--iters 200] [--rounds 3]
-  rocprofv3 --kernel-trace --stats -- python tools/moe_ffn_bench.py --trace T
+  python tools/moe_ffn_bench.py [--iters 200] [--rounds 3] [--w-fp8]
+  rocprofv3 --kernel-trace --stats -- python tools/moe_ffn_bench.py --trace T [--w-fp8]
 
---trace T runs 40 fused forwards at T tokens and prints the number of live
-experts of each input, from which the bytes the two streaming kernels had to
-read follow (gate/up: live * 2 * f * h * 2 B, down: live * h * f * 2 B)."""
+--w-fp8 times three paths the same way: a copy of the module on weight-only
+fp8 experts (MoEMLP.quantize_experts_fp8_) through ops.moe_ffn_fp8w and
+through its fallback loop of ops.linear_fp8w, and the bf16 module's fused path
+as the baseline for time.
+
+--trace T runs 40 fused forwards at T tokens (on the fp8 experts with --w-fp8)
+and prints the number of live experts of each input, from which the bytes the
+two streaming kernels had to read follow (gate/up: live * 2 * f * h * B, down:
+live * h * f * B, B = 2 bytes per bf16 weight, 1 per fp8 code)."""
 import argparse
+import copy
 import json
 import sys
 from pathlib import Path
@@ -22,6 +29,7 @@ from hypha_amd.models.moe import PRESETS, MoEMLP
 
 DEV = torch.device("cuda", 0)
 N_INPUTS = 8
+LIMITS = ("fused_ffn_max_tokens", "fused_ffn_fp8_max_tokens")
 
 
 def build():
@@ -45,7 +53,8 @@ def inputs(t):
 
 @torch.no_grad()
 def time_us(mlp, xs, fused, iters):
-    mlp.cfg.fused_ffn_max_tokens = (1 << 30) if fused else 0
+    for name in LIMITS:
+        setattr(mlp.cfg, name, (1 << 30) if fused else 0)
     for x in xs:
         mlp(x)
     start, end = (torch.cuda.Event(enable_timing=True) for _ in range(2))
@@ -63,31 +72,48 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--trace", type=int, default=0)
+    ap.add_argument("--w-fp8", action="store_true")
     args = ap.parse_args()
     mlp = build()
+    mlp8 = None
+    if args.w_fp8:
+        mlp8 = copy.deepcopy(mlp)  # its own cfg object too
+        mlp8.quantize_experts_fp8_()
     if args.trace:
         xs = inputs(args.trace)
+        run = mlp8 if args.w_fp8 else mlp
         with torch.no_grad():
             live = [len(set(mlp.router(x[0]).float().topk(2, -1).indices.reshape(-1).tolist()))
                     for x in xs]
             print(f"T={args.trace} live experts per input {live} mean {sum(live) / N_INPUTS}")
-            mlp.cfg.fused_ffn_max_tokens = 1 << 30
+            for name in LIMITS:
+                setattr(run.cfg, name, 1 << 30)
             for i in range(40):
-                mlp(xs[i % N_INPUTS])
+                run(xs[i % N_INPUTS])
         torch.cuda.synchronize()
         return
-    for t in (1, 2, 4, 8, 16, 32, 64, 128, 256, 512):
+    # (result key, module, fused path?)
+    paths = [("fused", mlp, True), ("loop", mlp, False)]
+    if args.w_fp8:
+        paths = [("fp8_fused", mlp8, True), ("fp8_loop", mlp8, False), ("bf16_fused", mlp, True)]
+    token_counts = (1, 2, 4, 8, 16, 32, 64, 128, 256, 512)
+    if args.w_fp8:  # the fp8 loop dequantises whole experts above 128 rows: look further
+        token_counts += (1024, 2048, 4096)
+    for t in token_counts:
         xs = inputs(t)
-        fused, loop = [], []
+        times = {key: [] for key, _, _ in paths}
         for _ in range(args.rounds):
-            fused.append(time_us(mlp, xs, True, args.iters))
-            loop.append(time_us(mlp, xs, False, args.iters))
+            for key, module, fused in paths:
+                times[key].append(time_us(module, xs, fused, args.iters))
         med = lambda v: sorted(v)[len(v) // 2]
-        print(json.dumps({"T": t, "fused_us": round(med(fused), 1),
-                          "loop_us": round(med(loop), 1),
-                          "fused_min_max": [round(min(fused), 1), round(max(fused), 1)],
-                          "loop_min_max": [round(min(loop), 1), round(max(loop), 1)]}),
-              flush=True)
+        row = {"T": t}
+        for key, v in times.items():
+            row[key + "_us"] = round(med(v), 1)
+            row[key + "_min_max"] = [round(min(v), 1), round(max(v), 1)]
+        if args.w_fp8:  # the rule that sets fused_ffn_fp8_max_tokens
+            row["fp8_fused_wins_every_round"] = all(
+                a < b for a, b in zip(times["fp8_fused"], times["fp8_loop"]))
+        print(json.dumps(row), flush=True)
 
 
 main()
