@@ -47,3 +47,4 @@ from .llama import LlamaConfig, LlamaForCausalLM  # noqa: E402,F401
 from .gpt2 import GPT2Config, GPT2ForCausalLM  # noqa: E402,F401
 from .moe import MoEConfig, MoEForCausalLM  # noqa: E402,F401
 from .fp8_linear import Fp8Linear, quantize_linears_fp8_  # noqa: E402,F401
+from .mxfp4_linear import Mxfp4Linear, quantize_linears_mxfp4_  # noqa: E402,F401

@@ -443,13 +443,18 @@ def _generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
     weight_quant="fp8" first turns the model's bias-free linears into
     weight-only fp8 ones, in place and once (models/fp8_linear.py: half the
     weight bytes per decoded token); it sits next to kv_quant and changes
-    nothing on a model that is already quantised."""
+    nothing on a model that is already quantised. weight_quant="mxfp4" does
+    the same with MXFP4 linears (models/mxfp4_linear.py: 4.25 bits per
+    weight)."""
     from .fp8_linear import check_weight_quant, quantize_linears_fp8_
     from .kv_cache import KVCache
+    from .mxfp4_linear import quantize_linears_mxfp4_
 
     check_weight_quant(weight_quant)
     if weight_quant == "fp8":
         quantize_linears_fp8_(self)
+    elif weight_quant == "mxfp4":
+        quantize_linears_mxfp4_(self)
     check_sampler(sampler, temperature, top_p, seed)
     if prefill_chunk is not None and prefill_chunk < 1:
         raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")

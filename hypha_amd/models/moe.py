@@ -468,13 +468,18 @@ class MoEForCausalLM(nn.Module):
         prompt in pieces of at most that many tokens; None = one pass.
         weight_quant="fp8" first turns the bias-free linears and the experts
         into weight-only fp8 ones, in place and once (models/fp8_linear.py);
-        it changes nothing on a model that is already quantised."""
+        it changes nothing on a model that is already quantised.
+        weight_quant="mxfp4" turns the bias-free linears into MXFP4 ones
+        (models/mxfp4_linear.py); the experts stay bf16 on the fused path."""
         from .fp8_linear import check_weight_quant, quantize_linears_fp8_
         from .kv_cache import KVCache
+        from .mxfp4_linear import quantize_linears_mxfp4_
 
         check_weight_quant(weight_quant)
         if weight_quant == "fp8":
             quantize_linears_fp8_(self)
+        elif weight_quant == "mxfp4":
+            quantize_linears_mxfp4_(self)
         if prefill_chunk is not None and prefill_chunk < 1:
             raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
         self.eval()

@@ -1,0 +1,58 @@
+"""Weight-only MXFP4 linears for serving: each weight is an e2m1 code, two per
+byte, with one E8M0 power-of-two scale per 32 consecutive inputs of a row
+(ops.quantize_mxfp4, the OCP microscaling format), 4.25 bits per weight
+against bf16's 16, and applied by ops.linear_mxfp4w: the weight-streaming HIP
+kernel for decode-sized batches, dequantise + library for prefill. Inference
+only."""
+
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from hypha_amd import ops
+
+
+class Mxfp4Linear(nn.Module):
+    """Bias-free linear on codes (uint8 [out, in / 2]) and scales (uint8
+    [out, in / 32]); W = ops.dequantize_mxfp4(codes, scales). Both buffers are
+    integers, so .to(dtype) and .bfloat16() only ever move them."""
+
+    def __init__(self, codes: torch.Tensor, scales: torch.Tensor):
+        super().__init__()
+        self.out_features, self.in_features = codes.shape[0], 2 * codes.shape[1]
+        self.register_buffer("codes", codes)
+        self.register_buffer("scales", scales)
+
+    @classmethod
+    @torch.no_grad()
+    def from_linear(cls, lin: nn.Linear) -> "Mxfp4Linear":
+        if lin.bias is not None:
+            raise ValueError("Mxfp4Linear has no bias")
+        return cls(*ops.quantize_mxfp4(lin.weight.detach()))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return ops.linear_mxfp4w(x, self.codes, self.scales)
+
+    def extra_repr(self) -> str:
+        return f"in_features={self.in_features}, out_features={self.out_features}"
+
+
+@torch.no_grad()
+def quantize_linears_mxfp4_(model: nn.Module) -> nn.Module:
+    """Replace, in place, every bias-free nn.Linear whose shape
+    ops/hip/linear_mxfp4w.hip serves by an Mxfp4Linear (in the Llama family:
+    wq, wk, wv, wo, w_gate, w_up, w_down and an untied lm_head). A linear that
+    shares its weight with an embedding (a tied head), one with a bias and one
+    of another shape stay as they are: the rules of quantize_linears_fp8_. The
+    experts of a MoEMLP are not linears and stay bf16 on the fused
+    ops.moe_ffn path; there is no MXFP4 expert kernel yet. Returns the model
+    in eval mode."""
+    tied = {id(m.weight) for m in model.modules() if isinstance(m, nn.Embedding)}
+    for parent in list(model.modules()):
+        for name, child in list(parent.named_children()):
+            if (isinstance(child, nn.Linear) and child.bias is None
+                    and id(child.weight) not in tied
+                    and ops.linear_mxfp4w_native_shapes(*child.weight.shape)):
+                setattr(parent, name, Mxfp4Linear.from_linear(child))
+    return model.eval()

@@ -61,6 +61,7 @@ from .interface import (  # noqa: E402
     attn_prefill,
     attn_prefill_paged,
     cross_entropy_loss,
+    dequantize_mxfp4,
     extract_delta,
     flash_attention,
     fused_adamw,
@@ -70,11 +71,14 @@ from .interface import (  # noqa: E402
     layernorm,
     linear_fp8w,
     linear_fp8w_native_shapes,
+    linear_mxfp4w,
+    linear_mxfp4w_native_shapes,
     linear_skinny,
     moe_ffn,
     moe_ffn_fp8w,
     moe_ffn_native_shapes,
     philox_uniform,
+    quantize_mxfp4,
     quantize_rows_e4m3,
     rmsnorm,
     sample_token,
@@ -107,6 +111,10 @@ __all__ = [
     "linear_fp8w",
     "linear_fp8w_native_shapes",
     "quantize_rows_e4m3",
+    "linear_mxfp4w",
+    "linear_mxfp4w_native_shapes",
+    "quantize_mxfp4",
+    "dequantize_mxfp4",
     "extract_delta",
     "sample_token",
     "philox_uniform",

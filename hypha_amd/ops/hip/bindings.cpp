@@ -164,6 +164,8 @@ torch::Tensor moe_ffn_fp8w(torch::Tensor x, torch::Tensor router_logits, torch::
                            torch::Tensor w_down8, torch::Tensor s_down, long top_k);
 // linear_fp8w.hip (weight-only e4m3 linear for decode-sized batches)
 torch::Tensor linear_fp8w(torch::Tensor x, torch::Tensor w8, torch::Tensor scale);
+// linear_mxfp4w.hip (weight-only MXFP4 linear for decode-sized batches)
+torch::Tensor linear_mxfp4w(torch::Tensor x, torch::Tensor codes, torch::Tensor scales);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adamw_step_", &adamw_step_);
@@ -230,4 +232,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_ffn", &moe_ffn);
   m.def("moe_ffn_fp8w", &moe_ffn_fp8w);
   m.def("linear_fp8w", &linear_fp8w);
+  m.def("linear_mxfp4w", &linear_mxfp4w);
 }

@@ -32,6 +32,7 @@ The HIP extension ABI (hypha_amd._C):
                top_k) -> bf16 [T, h]
   moe_route(router_logits_f32, top_k) -> (topi_i32, topw_f32, offsets_i32, pairs_i32)
   linear_fp8w(x_bf16 [M, K], w8_e4m3 [N, K], scale_f32 [N]) -> bf16 [M, N]
+  linear_mxfp4w(x_bf16 [M, K], codes_u8 [N, K / 2], scales_u8 [N, K / 32]) -> bf16 [M, N]
 """
 
 from __future__ import annotations
@@ -657,6 +658,88 @@ def linear_fp8w(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor,
                                scale.contiguous())
         return out.view(*x.shape[:-1], n)
     return reference.linear_fp8w(x, w8, scale)
+
+
+# ---------------------------------------------------------------------------
+# Weight-only MXFP4 linear (decode-sized batches)
+# ---------------------------------------------------------------------------
+
+# ops.linear_mxfp4w runs the native kernel for at most this many rows; larger
+# batches dequantise and go through the library. 128 is the largest M measured,
+# and there the kernel is still far ahead of that fallback on Llama-3-8B's
+# gate/up shape (81 us against 1515 us, most of it the PyTorch dequantiser;
+# profiles/linear_mxfp4w.md). No crossover was found; larger M was not measured
+LINEAR_MXFP4W_MAX_ROWS = 128
+
+
+@torch.no_grad()
+def quantize_mxfp4(w: torch.Tensor):
+    """OCP MXFP4 of w [..., K], K % 32 == 0 -> (codes uint8 [..., K / 2],
+    scales uint8 [..., K / 32]). Each block of 32 consecutive k shares the
+    power-of-two scale 2^e, e = floor(log2(amax)) - 2 clamped to [-125, 125]
+    (a block of zeros takes -125), stored as the E8M0 byte e + 127. The
+    elements over 2^e saturate at magnitude 6 and round to the nearest e2m1
+    value {0, 0.5, 1, 1.5, 2, 3, 4, 6}, ties to the even code; the code is
+    sign << 3 | index, zero always 0x0. Element 2 i is the low nibble of byte
+    i, element 2 i + 1 the high one (torch.float4_e2m1fn_x2's order). The
+    clamp keeps every dequantised value a normal, finite bf16."""
+    if not w.is_floating_point() or w.dim() < 1 or w.shape[-1] % 32 != 0:
+        raise ValueError("quantize_mxfp4: w must be floating point [..., K] with K % 32 == 0")
+    blocks = w.float().reshape(*w.shape[:-1], w.shape[-1] // 32, 32)
+    amax = blocks.abs().amax(-1)
+    # frexp: amax = m 2^ex with m in [0.5, 1), so floor(log2(amax)) = ex - 1
+    e = (torch.frexp(amax).exponent - 3).clamp(-125, 125)
+    e = torch.where(amax > 0, e, torch.full_like(e, -125))
+    a = (blocks * reference.pow2_f32(-e).unsqueeze(-1)).abs()
+    # index = how many midpoints lie below a; a tie stays at the even index
+    idx = torch.zeros_like(a, dtype=torch.uint8)
+    for i in range(7):
+        mid = (reference.E2M1_VALUES[i] + reference.E2M1_VALUES[i + 1]) / 2
+        idx += (a > mid) if i % 2 == 0 else (a >= mid)
+    nib = (idx | ((blocks < 0) & (idx > 0)).to(torch.uint8) << 3).reshape(
+        *w.shape[:-1], w.shape[-1] // 2, 2)
+    return nib[..., 0] | nib[..., 1] << 4, (e + 127).to(torch.uint8)
+
+
+dequantize_mxfp4 = reference.dequantize_mxfp4
+
+
+def linear_mxfp4w_native_shapes(n: int, k: int) -> bool:
+    """The weight shapes [N, K] ops/hip/linear_mxfp4w.hip serves."""
+    return k >= 128 and k % 128 == 0 and n >= 32 and n % 32 == 0
+
+
+@torch.no_grad()
+def linear_mxfp4w(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
+                  max_rows: int | None = None) -> torch.Tensor:
+    """Linear layer on weight-only MXFP4 weights: x [..., K], codes uint8
+    [N, K / 2] and scales uint8 [N, K / 32] as ops.quantize_mxfp4(W [N, K])
+    produces them -> [..., N] in x's dtype, equal to x . W'^T with
+    W' = ops.dequantize_mxfp4(codes, scales) and fp32 accumulation. Every
+    dequantised value is a bf16 value, so nothing is rounded before the GEMM.
+    The leading dims flatten to M rows. On the GPU, bf16 x with
+    M <= max_rows (default LINEAR_MXFP4W_MAX_ROWS), K % 128 == 0 and
+    N % 32 == 0 runs the weight-streaming MFMA kernel (ops/hip/
+    linear_mxfp4w.hip): the codes are converted and scaled in registers by
+    v_cvt_scalef32_pk_bf16_fp4, split-K is sized by the shapes alone (safe to
+    capture in a graph), no float atomics (bit-reproducible). Every other case
+    takes reference.linear_mxfp4w (dequantise, then the library). No autograd."""
+    if codes.dim() != 2 or codes.dtype != torch.uint8:
+        raise ValueError("linear_mxfp4w: codes must be uint8 [N, K / 2]")
+    n, k = codes.shape[0], 2 * codes.shape[1]
+    if scales.dtype != torch.uint8 or k % 32 != 0 or tuple(scales.shape) != (n, k // 32):
+        raise ValueError(f"linear_mxfp4w: scales must be uint8 [{n}, K / 32] with K = {k}")
+    if x.dim() < 1 or x.shape[-1] != k or not x.is_floating_point():
+        raise ValueError(f"linear_mxfp4w: x must be floating point [..., {k}]")
+    if max_rows is None:
+        max_rows = LINEAR_MXFP4W_MAX_ROWS
+    m = x.numel() // k
+    if (use_native(x) and x.dtype == torch.bfloat16 and 1 <= m <= max_rows
+            and linear_mxfp4w_native_shapes(n, k)):
+        out = _c().linear_mxfp4w(x.reshape(m, k).contiguous(), codes.contiguous(),
+                                 scales.contiguous())
+        return out.view(*x.shape[:-1], n)
+    return reference.linear_mxfp4w(x, codes, scales)
 
 
 # ---------------------------------------------------------------------------

@@ -176,6 +176,43 @@ def linear_fp8w(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor) -> torch
     return ((x @ w8.to(x.dtype).t()).float() * scale).to(x.dtype)
 
 
+# the e2m1 magnitudes by code index; an MXFP4 code is sign << 3 | index
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def pow2_f32(e: torch.Tensor) -> torch.Tensor:
+    """fp32 2^e for integer e in [-126, 127], built in the exponent field."""
+    return ((e.to(torch.int32) + 127) << 23).view(torch.float32)
+
+
+@torch.no_grad()
+def dequantize_mxfp4(codes: torch.Tensor, scales: torch.Tensor,
+                     dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """The values of MXFP4 codes uint8 [..., K / 2] (two e2m1 per byte, element
+    2 i in the low nibble of byte i) and E8M0 scales uint8 [..., K / 32], as
+    ops.quantize_mxfp4 produces them -> [..., K] in dtype:
+    e2m1(code) * 2^(scale - 127), exactly (every value is a bf16 value)."""
+    if (codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.dim() < 1
+            or codes.shape[:-1] != scales.shape[:-1]
+            or codes.shape[-1] != 16 * scales.shape[-1]):
+        raise ValueError("dequantize_mxfp4: codes must be uint8 [..., K / 2] and scales uint8 "
+                         "[..., K / 32]")
+    nib = torch.stack((codes & 0xf, codes >> 4), -1).reshape(*scales.shape, 32).to(torch.int32)
+    # E2M1_VALUES by arithmetic (no table to copy to the device, so the call can
+    # be captured in a graph): index i >= 2 is (2 + (i & 1)) 2^(i >> 1) / 4
+    idx = nib & 7
+    mag = torch.where(idx < 2, idx * 0.5, ((2 + (idx & 1)) << (idx >> 1)) * 0.25)
+    vals = torch.where(nib < 8, mag, -mag) * pow2_f32(scales.to(torch.int32) - 127).unsqueeze(-1)
+    return vals.reshape(*codes.shape[:-1], 2 * codes.shape[-1]).to(dtype)
+
+
+def linear_mxfp4w(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """Weight-only MXFP4 linear: x [..., K], codes uint8 [N, K / 2], scales
+    uint8 [N, K / 32] -> [..., N] in x's dtype. The dequantised weights are
+    exact in bf16 and fp32, so the GEMM runs on exact weights."""
+    return x @ dequantize_mxfp4(codes, scales, x.dtype).t()
+
+
 def moe_ffn_fp8w(x: torch.Tensor, router_logits: torch.Tensor, w_gate8: torch.Tensor,
                  s_gate: torch.Tensor, w_up8: torch.Tensor, s_up: torch.Tensor,
                  w_down8: torch.Tensor, s_down: torch.Tensor, top_k: int) -> torch.Tensor:

@@ -46,6 +46,7 @@ from hypha_amd import ops
 from hypha_amd.models.fp8_linear import Fp8Linear
 from hypha_amd.models.kv_cache import KVCache
 from hypha_amd.models.llama import RaggedStep, check_prompt_lens, prefill_ragged
+from hypha_amd.models.mxfp4_linear import Mxfp4Linear
 from hypha_amd.models.paged_kv import PagedKVCache, PageTable, pages_for
 
 
@@ -130,13 +131,14 @@ class GraphedDecoder:
         on these shapes — shuffle-reduction issue-bound; kept as an opt-in
         negative result like grouped_gemm). A weight-only fp8 linear
         (models/fp8_linear.py) runs its own module instead: ops.linear_fp8w,
-        the kernel of ops/hip/linear_fp8w.hip at these batch sizes."""
+        the kernel of ops/hip/linear_fp8w.hip at these batch sizes; so does
+        a weight-only MXFP4 linear (models/mxfp4_linear.py, ops.linear_mxfp4w)."""
         m = self.model
         cfg = m.cfg
         b = self.batch
 
         def lin(t, mod):
-            if isinstance(mod, Fp8Linear):
+            if isinstance(mod, (Fp8Linear, Mxfp4Linear)):
                 return mod(t)
             return t @ mod.weight.t()
 
@@ -182,7 +184,7 @@ class GraphedDecoder:
         set the next input token."""
         m = self.model
         x = m.norm(x)
-        if isinstance(m.lm_head, Fp8Linear):
+        if isinstance(m.lm_head, (Fp8Linear, Mxfp4Linear)):
             logits = m.lm_head(x[:, 0])
         else:
             head_w = m.lm_head.weight if m.lm_head is not None else m.embed.weight

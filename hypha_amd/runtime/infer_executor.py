@@ -12,7 +12,7 @@ so the scheduler's FSM and lease machinery apply unchanged.
 Job config: {"model", "data": <fetch ref>, "results": <send ref>?,
              "max_new_tokens", "batch_size", "seq_len", "temperature",
              "top_k", "top_p"?, "sampler": "philox"?, "seed"?,
-             "num_batches", "kv_cache": "fp8"?, "weight_quant": "fp8"?,
+             "num_batches", "kv_cache": "fp8"?, "weight_quant": "fp8" | "mxfp4"?,
              "prefill_chunk": <int>?, "pad_token_id": <int>?,
              "eos_token_id": <int>?, "kv_layout": "paged"?, "kv_pages": <int>?}
 
@@ -26,7 +26,9 @@ temperature samples with torch.multinomial on the eager path. "kv_cache": "fp8" 
 (activation memory bounded by the chunk; absent = one pass).
 "weight_quant": "fp8" quantises the bias-free linears once after load to
 weight-only e4m3 with per-row scales (models/fp8_linear.py), halving the
-weight bytes a decode step reads; any other value is an error.
+weight bytes a decode step reads; "weight_quant": "mxfp4" quantises them to
+MXFP4 instead (models/mxfp4_linear.py: e2m1 codes with one power-of-two scale
+per 32 inputs, 4.25 bits per weight); any other value is an error.
 
 "pad_token_id" makes every batch RAGGED: prompts are right-padded rows, a
 prompt's length is its row without the trailing run of that id (at least one
@@ -62,7 +64,7 @@ def prompt_lengths(prompts: torch.Tensor, pad_token_id: int) -> torch.Tensor:
 
 
 def weight_quant(cfg: dict):
-    """The job's "weight_quant": None or "fp8"; anything else raises."""
+    """The job's "weight_quant": None, "fp8" or "mxfp4"; anything else raises."""
     from hypha_amd.models.fp8_linear import check_weight_quant
 
     check_weight_quant(cfg.get("weight_quant"))
@@ -109,6 +111,8 @@ def main() -> int:
     model.eval()
     if wq == "fp8":
         models.quantize_linears_fp8_(model)
+    elif wq == "mxfp4":
+        models.quantize_linears_mxfp4_(model)
 
     batch_size =int(cfg.get("batch_size", 1))
     seq_len = int(cfg.get("seq_len", 64))

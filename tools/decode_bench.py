@@ -42,6 +42,9 @@ def main():
     p.add_argument("--w-fp8", action="store_true",
                    help="weight-only fp8 linears (e4m3 + per-row scales, "
                         "ops.linear_fp8w)")
+    p.add_argument("--w-mxfp4", action="store_true",
+                   help="weight-only MXFP4 linears (e2m1 codes + one E8M0 scale "
+                        "per 32 inputs, ops.linear_mxfp4w)")
     p.add_argument("--ragged", metavar="LO:HI", default=None,
                    help="right-padded batch: prompt lengths drawn uniformly "
                         "from [LO, HI] (fixed seed, HI <= --prefill), generated "
@@ -54,6 +57,8 @@ def main():
     args = p.parse_args()
     if args.paged and not (args.graph and args.ragged is not None):
         raise SystemExit("--paged needs --graph --ragged LO:HI")
+    if args.w_fp8 and args.w_mxfp4:
+        raise SystemExit("--w-fp8 and --w-mxfp4 exclude each other")
 
     from hypha_amd import models
 
@@ -69,6 +74,8 @@ def main():
             buf.data = buf.data.float()
     if args.w_fp8:
         models.quantize_linears_fp8_(model)
+    if args.w_mxfp4:
+        models.quantize_linears_mxfp4_(model)
     ids = torch.randint(0, model.cfg.vocab_size - 1, (args.batch, args.prefill),
                         device=dev)
 
@@ -108,7 +115,7 @@ def main():
 
         gen = functools.partial(model.generate, kv_quant=kvq)
 
-    tag = " w-fp8" if args.w_fp8 else ""
+    tag = " w-fp8" if args.w_fp8 else " w-mxfp4" if args.w_mxfp4 else ""
     if args.sample is not None:
         import functools
 
