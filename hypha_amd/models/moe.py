@@ -34,6 +34,12 @@ class MoEConfig(LlamaConfig):
     # 128 rows. The largest measured count at which the fused path won every
     # round (3.8 against 5.1 ms; it loses at 2048), profiles/moe_ffn_fp8w.md
     fused_ffn_fp8_max_tokens: int = 1024
+    # the same limit for weight-only MXFP4 experts: ops.moe_ffn_mxfp4w against
+    # the per-expert ops.linear_mxfp4w loop, which dequantises whole experts in
+    # PyTorch above 128 rows. By the same rule: the fused path won every round
+    # at every measured count, and 4096 is the largest one measured (7.5
+    # against 39 ms; profiles/moe_ffn_mxfp4w.md, section 1)
+    fused_ffn_mxfp4_max_tokens: int = 4096
 
     def num_params(self) -> int:
         h, v, f = self.hidden_size, self.vocab_size, self.ffn_hidden
@@ -146,6 +152,8 @@ class MoEMLP(nn.Module):
         the module in eval mode."""
         if self.ep is not None:
             raise ValueError("quantize_experts_fp8_: expert-parallel experts are not supported")
+        if self.experts_mxfp4:
+            raise ValueError("quantize_experts_fp8_: the experts are already MXFP4")
         if not self.experts_fp8:
             for name in ("gate", "up", "down"):
                 w = getattr(self, "w_" + name).detach()
@@ -154,6 +162,36 @@ class MoEMLP(nn.Module):
                 del w
                 self.register_buffer(f"w_{name}8", torch.stack([c for c, _ in q]))
                 self.register_buffer(f"s_{name}", torch.stack([s for _, s in q]))
+        return self.eval()
+
+    # buffers of a module with weight-only MXFP4 experts: codes [E, f, h / 2],
+    # [E, f, h / 2], [E, h, f / 2] and one E8M0 scale byte per 32 inputs of a
+    # row, all uint8, so .to(dtype) and .bfloat16() only ever move them
+    _MXFP4_BUFFERS = ("c_gate", "e_gate", "c_up", "e_up", "c_down", "e_down")
+
+    @property
+    def experts_mxfp4(self) -> bool:
+        return "c_gate" in self._buffers
+
+    @torch.no_grad()
+    def quantize_experts_mxfp4_(self) -> "MoEMLP":
+        """Replace the three expert parameters by MXFP4 codes and E8M0 block
+        scales (ops.quantize_mxfp4): 4.25 bits per weight against bf16's 16,
+        served by ops.moe_ffn_mxfp4w at decode sizes and by ops.linear_mxfp4w
+        per expert above them. Inference only; a second call changes nothing.
+        Returns the module in eval mode."""
+        if self.ep is not None:
+            raise ValueError("quantize_experts_mxfp4_: expert-parallel experts are not supported")
+        if self.experts_fp8:
+            raise ValueError("quantize_experts_mxfp4_: the experts are already fp8")
+        if not self.experts_mxfp4:
+            for name in ("gate", "up", "down"):
+                w = getattr(self, "w_" + name).detach()
+                delattr(self, "w_" + name)
+                q = [ops.quantize_mxfp4(we) for we in w]  # an expert at a time: fp32 temps
+                del w
+                self.register_buffer(f"c_{name}", torch.stack([c for c, _ in q]))
+                self.register_buffer(f"e_{name}", torch.stack([s for _, s in q]))
         return self.eval()
 
     def _apply(self, fn, recurse=True):
@@ -180,11 +218,21 @@ class MoEMLP(nn.Module):
             if self.training or torch.is_grad_enabled():
                 raise RuntimeError("MoEMLP: fp8 experts serve inference only "
                                    "(eval mode under torch.no_grad())")
-            if self._use_fused_ffn_fp8(xf):
+            if self._use_fused_ffn_quant(xf, cfg.fused_ffn_fp8_max_tokens):
                 # the same device-routed path on one byte per weight
                 out = ops.moe_ffn_fp8w(xf.contiguous(), logits, self.w_gate8, self.s_gate,
                                        self.w_up8, self.s_up, self.w_down8, self.s_down,
                                        cfg.top_k)
+                return out.reshape(b, s, h), xf.new_zeros(())
+        elif self.experts_mxfp4:
+            if self.training or torch.is_grad_enabled():
+                raise RuntimeError("MoEMLP: MXFP4 experts serve inference only "
+                                   "(eval mode under torch.no_grad())")
+            if self._use_fused_ffn_quant(xf, cfg.fused_ffn_mxfp4_max_tokens):
+                # the same device-routed path on 4.25 bits per weight
+                out = ops.moe_ffn_mxfp4w(xf.contiguous(), logits, self.c_gate, self.e_gate,
+                                         self.c_up, self.e_up, self.c_down, self.e_down,
+                                         cfg.top_k)
                 return out.reshape(b, s, h), xf.new_zeros(())
         elif self._use_fused_ffn(xf):
             # inference at decode sizes: routing, grouping and the expert
@@ -230,6 +278,7 @@ class MoEMLP(nn.Module):
 
         use_native_grouped = (
             os.environ.get("HYPHA_NATIVE_GROUPED", "0") == "1" and not self.experts_fp8
+            and not self.experts_mxfp4
             and not torch.is_grad_enabled() and gathered.is_cuda
             and gathered.dtype == torch.bfloat16 and ops.has_native()
             and cfg.ffn_hidden % 128 == 0 and cfg.hidden_size % 128 == 0
@@ -269,12 +318,13 @@ class MoEMLP(nn.Module):
                                           cfg.n_experts, cfg.top_k)
         )
 
-    def _use_fused_ffn_fp8(self, xf: torch.Tensor) -> bool:
-        """_use_fused_ffn for fp8 experts (the caller has checked eval mode and
-        no_grad); HYPHA_NATIVE_GROUPED has no meaning for them."""
+    def _use_fused_ffn_quant(self, xf: torch.Tensor, max_tokens: int) -> bool:
+        """_use_fused_ffn for fp8 or MXFP4 experts, up to their own limit (the
+        caller has checked eval mode and no_grad); HYPHA_NATIVE_GROUPED has no
+        meaning for them."""
         cfg = self.cfg
         return (
-            self.ep is None and xf.shape[0] <= cfg.fused_ffn_fp8_max_tokens
+            self.ep is None and xf.shape[0] <= max_tokens
             and xf.dtype == torch.bfloat16 and ops.use_native(xf)
             and ops.moe_ffn_native_shapes(cfg.hidden_size, cfg.ffn_hidden,
                                           cfg.n_experts, cfg.top_k)
@@ -283,7 +333,8 @@ class MoEMLP(nn.Module):
     def _expert_ffn(self, xs: torch.Tensor, counts: list[int]) -> torch.Tensor:
         """Per-expert SwiGLU chains over expert-grouped rows (local shard). On
         fp8 experts every projection is an ops.linear_fp8w: its kernel up to
-        128 rows per expert, dequantise and the library beyond."""
+        128 rows per expert, dequantise and the library beyond; on MXFP4
+        experts an ops.linear_mxfp4w, by the same rule."""
         out_groups = []
         start = 0
         for e in range(len(counts)):
@@ -296,6 +347,11 @@ class MoEMLP(nn.Module):
                 ue = ops.linear_fp8w(xe, self.w_up8[e], self.s_up[e])
                 he = ops.swiglu(ge, ue)
                 out_groups.append(ops.linear_fp8w(he, self.w_down8[e], self.s_down[e]))
+            elif self.experts_mxfp4:
+                ge = ops.linear_mxfp4w(xe, self.c_gate[e], self.e_gate[e])
+                ue = ops.linear_mxfp4w(xe, self.c_up[e], self.e_up[e])
+                he = ops.swiglu(ge, ue)
+                out_groups.append(ops.linear_mxfp4w(he, self.c_down[e], self.e_down[e]))
             else:
                 ge = xe @ self.w_gate[e].t()
                 ue = xe @ self.w_up[e].t()
@@ -469,8 +525,8 @@ class MoEForCausalLM(nn.Module):
         weight_quant="fp8" first turns the bias-free linears and the experts
         into weight-only fp8 ones, in place and once (models/fp8_linear.py);
         it changes nothing on a model that is already quantised.
-        weight_quant="mxfp4" turns the bias-free linears into MXFP4 ones
-        (models/mxfp4_linear.py); the experts stay bf16 on the fused path."""
+        weight_quant="mxfp4" does the same with MXFP4 linears and experts
+        (models/mxfp4_linear.py)."""
         from .fp8_linear import check_weight_quant, quantize_linears_fp8_
         from .kv_cache import KVCache
         from .mxfp4_linear import quantize_linears_mxfp4_

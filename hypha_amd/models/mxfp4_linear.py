@@ -2,8 +2,9 @@
 byte, with one E8M0 power-of-two scale per 32 consecutive inputs of a row
 (ops.quantize_mxfp4, the OCP microscaling format), 4.25 bits per weight
 against bf16's 16, and applied by ops.linear_mxfp4w: the weight-streaming HIP
-kernel for decode-sized batches, dequantise + library for prefill. Inference
-only."""
+kernel for decode-sized batches, dequantise + library for prefill. The experts
+of the MoE family are quantised the same way by MoEMLP.quantize_experts_mxfp4_
+and applied by ops.moe_ffn_mxfp4w. Inference only."""
 
 from __future__ import annotations
 
@@ -45,9 +46,12 @@ def quantize_linears_mxfp4_(model: nn.Module) -> nn.Module:
     wq, wk, wv, wo, w_gate, w_up, w_down and an untied lm_head). A linear that
     shares its weight with an embedding (a tied head), one with a bias and one
     of another shape stay as they are: the rules of quantize_linears_fp8_. The
-    experts of a MoEMLP are not linears and stay bf16 on the fused
-    ops.moe_ffn path; there is no MXFP4 expert kernel yet. Returns the model
-    in eval mode."""
+    experts of every MoEMLP whose shapes ops.moe_ffn_mxfp4w serves are
+    quantised the same way (MoEMLP.quantize_experts_mxfp4_); its router is a
+    linear like any other (with 8 outputs it is of another shape and stays
+    bf16). Returns the model in eval mode."""
+    from .moe import MoEMLP
+
     tied = {id(m.weight) for m in model.modules() if isinstance(m, nn.Embedding)}
     for parent in list(model.modules()):
         for name, child in list(parent.named_children()):
@@ -55,4 +59,8 @@ def quantize_linears_mxfp4_(model: nn.Module) -> nn.Module:
                     and id(child.weight) not in tied
                     and ops.linear_mxfp4w_native_shapes(*child.weight.shape)):
                 setattr(parent, name, Mxfp4Linear.from_linear(child))
+        if isinstance(parent, MoEMLP) and ops.moe_ffn_native_shapes(
+                parent.cfg.hidden_size, parent.cfg.ffn_hidden, parent.cfg.n_experts,
+                parent.cfg.top_k):
+            parent.quantize_experts_mxfp4_()
     return model.eval()

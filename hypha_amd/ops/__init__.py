@@ -76,6 +76,7 @@ from .interface import (  # noqa: E402
     linear_skinny,
     moe_ffn,
     moe_ffn_fp8w,
+    moe_ffn_mxfp4w,
     moe_ffn_native_shapes,
     philox_uniform,
     quantize_mxfp4,
@@ -120,5 +121,6 @@ __all__ = [
     "philox_uniform",
     "moe_ffn",
     "moe_ffn_fp8w",
+    "moe_ffn_mxfp4w",
     "moe_ffn_native_shapes",
 ]

@@ -162,6 +162,9 @@ torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor router_logits, torch::Tenso
 torch::Tensor moe_ffn_fp8w(torch::Tensor x, torch::Tensor router_logits, torch::Tensor w_gate8,
                            torch::Tensor s_gate, torch::Tensor w_up8, torch::Tensor s_up,
                            torch::Tensor w_down8, torch::Tensor s_down, long top_k);
+torch::Tensor moe_ffn_mxfp4w(torch::Tensor x, torch::Tensor router_logits, torch::Tensor c_gate,
+                             torch::Tensor e_gate, torch::Tensor c_up, torch::Tensor e_up,
+                             torch::Tensor c_down, torch::Tensor e_down, long top_k);
 // linear_fp8w.hip (weight-only e4m3 linear for decode-sized batches)
 torch::Tensor linear_fp8w(torch::Tensor x, torch::Tensor w8, torch::Tensor scale);
 // linear_mxfp4w.hip (weight-only MXFP4 linear for decode-sized batches)
@@ -231,6 +234,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_route", &moe_route);
   m.def("moe_ffn", &moe_ffn);
   m.def("moe_ffn_fp8w", &moe_ffn_fp8w);
+  m.def("moe_ffn_mxfp4w", &moe_ffn_mxfp4w);
   m.def("linear_fp8w", &linear_fp8w);
   m.def("linear_mxfp4w", &linear_mxfp4w);
 }

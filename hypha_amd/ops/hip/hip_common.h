@@ -66,6 +66,16 @@ __device__ __forceinline__ s16x8 e4m3x8_to_bf16x8(unsigned int d0, unsigned int 
   return __builtin_bit_cast(s16x8, v);
 }
 
+// eight e2m1 codes (one dword, k order = nibble order) times sc -> one bf16 MFMA operand
+__device__ __forceinline__ s16x8 e2m1x8_to_bf16x8(unsigned int d, float sc) {
+  u32x4 v;
+  v[0] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 0));
+  v[1] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 1));
+  v[2] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 2));
+  v[3] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 3));
+  return __builtin_bit_cast(s16x8, v);
+}
+
 // Grid sizing for memory-bound grid-stride kernels: cap at ~8 blocks/CU.
 inline int elementwise_grid(long long n_items, int block = 256) {
   long long blocks = (n_items + block - 1) / block;

@@ -62,18 +62,6 @@ constexpr int KC = 2 * KW;     // k per LDS chunk
 constexpr int PITCH = KC + 8;  // LDS row pitch (1040 B = 65 x 16 B: conflict-free b128 reads)
 constexpr int XL = KC * NT / (256 * 8);  // 16-byte activation loads per thread per chunk
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
-// eight e2m1 codes (one dword, k order = nibble order) times sc -> one bf16 MFMA operand
-__device__ __forceinline__ s16x8 e2m1x8_to_bf16x8(unsigned int d, float sc) {
-  u32x4 v;
-  v[0] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 0));
-  v[1] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 1));
-  v[2] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 2));
-  v[3] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 3));
-  return __builtin_bit_cast(s16x8, v);
-}
-
 // SPLIT = false: outp = out bf16 [M, N]. gridDim.y == 1.
 // SPLIT = true : outp = part fp32 [gridDim.y, M, N].
 template <bool SPLIT>

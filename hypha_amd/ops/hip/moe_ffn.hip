@@ -92,6 +92,48 @@
 // row tiles ask for 4 splits of 7 chunks, so 512 workgroups are live in the
 // down stage (one full residency of 256 CUs x 2) and 2 x 448 = 896 in
 // gate/up, out of 2048 and 3584 launched.
+//
+// Weight-only MXFP4 experts (moe_ffn_mxfp4w): the same five launches with
+// moe_expert_mxfp4w_kernel<DOWN, DEPTH>. The weights are e2m1 codes, two per
+// byte, with one E8M0 scale byte per 32 k of a row (ops.quantize_mxfp4 of the
+// 3-D weight). Every e2m1 value times a power of two is a bf16 value, so the
+// GEMMs are again bf16 MFMAs on exact operands. The scale belongs to a k block:
+// it enters at the conversion (v_cvt_scalef32_pk_bf16_fp4, e2m1x8_to_bf16x8 in
+// hip_common.h) inside the k loop, and the epilogues do no scaling. The
+// intermediate is one bf16 row per pair, hbuf [P, f] = bf16(silu(g) * u),
+// rounded once from fp32, 32 pairs on N in down, as in moe_expert_kernel: at
+// 4-bit weights that rounding is not what limits accuracy, and fp8w's hi/lo
+// pair of rows would halve the pairs per down tile.
+// The kernel keeps moe_expert_kernel's structure with linear_mxfp4w.hip's k
+// geometry:
+//   chunk   512 k (pitch 520, double-buffered activation stage, one barrier
+//           per chunk). The four waves split a chunk 2 by k x 2 by row tile:
+//           wave w takes k in [256 (w & 1), + 256) of tile w >> 1 (gate/up:
+//           tile 0 the gate rows and tile 1 the up rows of one f tile; down:
+//           two 32-row h tiles), one whole 128-byte line of each of its 32 rows
+//           and one accumulator. Lane (m, hi) of load j holds the 32 codes
+//           k = 64 j + 32 hi .. + 32: one MX block, one scale byte, four MFMA
+//           steps (dword d is k + 8 d .. + 8, B read from LDS at the same k).
+//           The two k-waves of a tile meet in LDS in wave order.
+//   depth   codes and scale dwords are loaded DEPTH chunks ahead into DEPTH + 1
+//           register sets; the chunk loop is unrolled over the sets, so a set
+//           is addressed by constants and never copied. Activations stay one
+//           chunk ahead (they go through LDS). DEPTH = 2 is 8 KiB of codes in
+//           flight per wave, 64 KiB per CU at two workgroups. It only holds if
+//           the weight loads carry no branch: with `if (k < Kd) load` the
+//           compiler cannot count the loads behind the one it needs and waits
+//           for vmcnt(0) before the MFMAs, so one chunk is in flight whatever
+//           DEPTH is (measured: DEPTH 2 was then 1 - 5 % slower than DEPTH 1).
+//           The loads are therefore unconditional and a half line past the row
+//           (K % 256 == 128) or a chunk past the split re-reads the row's
+//           first, cached 64 bytes; its MFMA steps are skipped load-uniformly.
+//           That version is 4 - 15 % faster than DEPTH 1
+//           (profiles/moe_ffn_mxfp4w.md, section 3).
+//   gather  as in the fp8w kernel: whole rows per wave, wave-uniform source
+//           row, slots past the count zeroed once per token tile and neither
+//           loaded nor stored afterwards.
+//   LDS     66560 B, 2 waves/SIMD (__launch_bounds__(256, 2)); 218 / 216 VGPR
+//           (gate/up / down), 0 AGPR, 0 scratch.
 
 #include <torch/extension.h>
 
@@ -555,6 +597,197 @@ __global__ __launch_bounds__(256, 2) void moe_expert_fp8w_kernel(
   }
 }
 
+// ---- expert GEMMs on weight-only MXFP4 experts ---------------------------------
+
+constexpr int KW4 = 256;         // k per wave per chunk: one 128-byte line of a code row
+constexpr int KC4 = 2 * KW4;     // k per LDS chunk
+constexpr int PITCH4 = KC4 + 8;  // LDS row pitch (1040 B = 65 x 16 B: conflict-free b128 reads)
+constexpr int XL4 = KC4 * NT / (256 * 8);  // 16-byte activation loads per thread per chunk
+// chunks of codes and scale bytes a wave keeps in flight ahead of its MFMAs
+#ifndef HYPHA_MOE_MXFP4_DEPTH
+#define HYPHA_MOE_MXFP4_DEPTH 2
+#endif
+
+// moe_expert_kernel on MXFP4 codes (two e2m1 per byte) with one E8M0 scale
+// byte per 32 k of a row.
+// DOWN = false: act = x [T, Kd], wa/wb = codes of W_gate/W_up [E, R, Kd / 2],
+//               sa/sb = their scales [E, R, Kd / 32]; the workgroup's two
+//               tiles are rows rows0 .. + 32 of gate and of up, out = hbuf
+//               bf16 [P, R].
+// DOWN = true : act = hbuf [P, Kd], wa/sa = codes/scales of W_down; the tiles
+//               are rows rows0 .. + 32 and rows0 + 32 .. + 32, out = ybuf fp32
+//               [gridDim.z, P, R]; split z takes the chunks [z * cps,
+//               (z + 1) * cps).
+template <bool DOWN, int DEPTH>
+__global__ __launch_bounds__(256, 2) void moe_expert_mxfp4w_kernel(
+    const short* __restrict__ act, const unsigned char* __restrict__ wa,
+    const unsigned char* __restrict__ wb, const unsigned char* __restrict__ sa,
+    const unsigned char* __restrict__ sb, const int* __restrict__ offsets,
+    const int* __restrict__ pairs, const float* __restrict__ topw,
+    void* __restrict__ outp, int Kd, int R, int top_k, int P, int cps) {
+  static_assert(DEPTH >= 1 && DEPTH <= 3, "prefetch depth");
+  constexpr int NS = DEPTH + 1;  // register sets: the chunk in use and DEPTH in flight
+  const int e = blockIdx.y;
+  const int off = offsets[e];
+  const int cnt = offsets[e + 1] - off;
+  if (cnt == 0) return;  // nobody chose this expert: no weight is read
+
+  __shared__ __attribute__((aligned(16))) short xs[2 * NT * PITCH4];
+  float* red = reinterpret_cast<float*>(xs);  // [4 waves][16][64] after the k loop
+  static_assert(4 * 16 * 64 * sizeof(float) <= sizeof(short) * 2 * NT * PITCH4,
+                "reduction image must fit the staging buffers");
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, w = tid >> 6;
+  const int ln = lane & 31, hi = lane >> 5;
+  const int kw = w & 1, rt = w >> 1;  // this wave's k half of a chunk and its row tile
+  const int rows0 = blockIdx.x * (DOWN ? 64 : 32);
+  // a row is Kd / 2 bytes of codes and Kd / 32 scale bytes
+  const long long row = (long long)e * R + rows0 + (DOWN ? 32 * rt : 0) + ln;
+  const unsigned char* ap = ((DOWN || rt == 0) ? wa : wb) + row * (Kd / 2) + 16 * hi;
+  const unsigned char* sp = ((DOWN || rt == 0) ? sa : sb) + row * (Kd / 32);
+  const int nc = (Kd + KC4 - 1) / KC4;
+  const int c0 = blockIdx.z * cps;
+  const int c1 = min(nc, c0 + cps);
+  const int xk = lane * 8;  // staging: k inside the chunk; wave w stages slots w + 4 i
+
+  for (int t0 = 0; t0 < cnt; t0 += NT) {
+    // activation row of each slot this wave stages (wave-uniform); a slot past
+    // the count is zeroed in both buffers here and never loaded or stored again
+    int rowi[XL4];
+#pragma unroll
+    for (int i = 0; i < XL4; ++i) {
+      const int s = t0 + w + 4 * i;
+      rowi[i] = -1;
+      if (s < cnt) {
+        rowi[i] = DOWN ? pairs[off + s] : pairs[off + s] / top_k;
+      } else {
+        *reinterpret_cast<s16x8*>(xs + (w + 4 * i) * PITCH4 + xk) = s16x8{};
+        *reinterpret_cast<s16x8*>(xs + (NT + w + 4 * i) * PITCH4 + xk) = s16x8{};
+      }
+    }
+    // a lane whose k lies past Kd (the last chunk of a Kd that is no multiple
+    // of KC4) stages zeros; the MFMA steps at that k are skipped anyway
+    auto load_x = [&](int c, s16x8(&xr)[XL4]) {
+      const int k = c * KC4 + xk;
+#pragma unroll
+      for (int i = 0; i < XL4; ++i) {
+        xr[i] = s16x8{};
+        if (rowi[i] >= 0 && k < Kd)
+          xr[i] = *reinterpret_cast<const s16x8*>(act + (long long)rowi[i] * Kd + k);
+      }
+    };
+    auto store_x = [&](int buf, const s16x8(&xr)[XL4]) {
+#pragma unroll
+      for (int i = 0; i < XL4; ++i)
+        if (rowi[i] >= 0)
+          *reinterpret_cast<s16x8*>(xs + (buf * NT + w + 4 * i) * PITCH4 + xk) = xr[i];
+    };
+    // this wave's 256 k of chunk c: one 128-byte line of each code row and its
+    // 8 scale bytes; lane (m, hi) of load j holds the 32 codes k = 64 j + 32 hi
+    // .. + 32, one MX block. Kd % 128 == 0, so loads 2 j and 2 j + 1 (128 k, 4
+    // scale bytes) are both inside the row or both past it. The loads carry no
+    // branch: a branch around a load makes the compiler wait for every load in
+    // flight (vmcnt(0)) before the MFMAs, which leaves one chunk in flight
+    // whatever DEPTH is. A half past the row, or a chunk at or past c1, reads
+    // the first 64 bytes of its own row and its first scale dword again (every
+    // row has them, they are in cache, and their MFMA steps are skipped): that
+    // is one line per row and at most DEPTH + 1 times per workgroup.
+    auto load_w = [&](int c, u32x4(&wr)[4], unsigned int(&sr)[2]) {
+      const int k = c * KC4 + kw * KW4;
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        const bool in = c < c1 && k + 128 * g < Kd;  // wave-uniform
+        const long long oc = in ? (long long)c * (KC4 / 2) + kw * (KW4 / 2) + 64 * g : 0;
+        const long long os = in ? (long long)c * (KC4 / 32) + kw * (KW4 / 32) + 4 * g : 0;
+        wr[2 * g] = *reinterpret_cast<const u32x4*>(ap + oc);
+        wr[2 * g + 1] = *reinterpret_cast<const u32x4*>(ap + oc + 32);
+        sr[g] = *reinterpret_cast<const unsigned int*>(sp + os);
+      }
+    };
+
+    f32x16 acc = {};
+    // set s holds chunk c0 + s, c0 + s + NS, ...: the loop below is unrolled
+    // over the sets, so every index is a constant and nothing is ever copied
+    u32x4 wr[NS][4] = {};
+    unsigned int sr[NS][2] = {};
+    s16x8 xr[XL4];
+    load_x(c0, xr);
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d) load_w(c0 + d, wr[d], sr[d]);
+    store_x(0, xr);
+    __syncthreads();
+    for (int cb = c0; cb < c1; cb += NS) {
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const int c = cb + s;
+        if (c < c1) {  // uniform over the workgroup
+          const int buf = (c - c0) & 1;
+          const bool more = c + 1 < c1;
+          if (more) load_x(c + 1, xr);
+          load_w(c + DEPTH, wr[(s + DEPTH) % NS], sr[(s + DEPTH) % NS]);
+          const int k = c * KC4 + kw * KW4;
+          const short* bp = xs + (buf * NT + ln) * PITCH4 + kw * KW4 + 32 * hi;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (k + 64 * j < Kd) {
+              // scale byte 2 j + hi of the wave's 8: 2^(byte - 127) as fp32
+              const float sc = __uint_as_float(
+                  ((sr[s][j >> 1] >> (16 * (j & 1) + 8 * hi)) & 0xffu) << 23);
+              // dword d of the load is k + 8 d .. + 8; B is read at the same k
+#pragma unroll
+              for (int d = 0; d < 4; ++d) {
+                const s16x8 b = *reinterpret_cast<const s16x8*>(bp + 64 * j + 8 * d);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                    e2m1x8_to_bf16x8(wr[s][j][d], sc), b, acc, 0, 0, 0);
+              }
+            }
+          }
+          if (more) store_x(buf ^ 1, xr);
+          __syncthreads();
+        }
+      }
+    }
+
+    // the two k-waves of each tile meet in LDS and are added in wave order
+#pragma unroll
+    for (int r = 0; r < 16; ++r) red[(w * 16 + r) * 64 + lane] = acc[r];
+    __syncthreads();
+    // thread (n, q): token n, tile rows 8 (q >> 1) + 4 (q & 1) .. + 4, which
+    // are registers 4 (q >> 1) .. + 4 of MFMA lane 32 (q & 1) + n
+    const int n = tid & 31, q = tid >> 5;
+    f32x4 s0, s1;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = 4 * (q >> 1) + i, src = 32 * (q & 1) + n;
+      s0[i] = red[(0 * 16 + r) * 64 + src] + red[(1 * 16 + r) * 64 + src];
+      s1[i] = red[(2 * 16 + r) * 64 + src] + red[(3 * 16 + r) * 64 + src];
+    }
+    if (t0 + n < cnt) {
+      const int p = pairs[off + t0 + n];
+      const int m = rows0 + 8 * (q >> 1) + 4 * (q & 1);
+      if (!DOWN) {  // s0 = gate, s1 = up; rounded to bf16 once
+        s16x4 o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = f2bf(s0[i] / (1.f + __expf(-s0[i])) * s1[i]);
+        *reinterpret_cast<s16x4*>(static_cast<short*>(outp) + (long long)p * R + m) = o;
+      } else {
+        const float wt = topw[p];
+        float* y = static_cast<float*>(outp) + ((long long)blockIdx.z * P + p) * R + m;
+        f32x4 y0, y1;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          y0[i] = s0[i] * wt;
+          y1[i] = s1[i] * wt;
+        }
+        *reinterpret_cast<f32x4*>(y) = y0;
+        *reinterpret_cast<f32x4*>(y + 32) = y1;
+      }
+    }
+    __syncthreads();  // red aliases the next token tile's staging buffers
+  }
+}
+
 // out[t, c .. c + 8] = bf16(sum_k (sum_s ybuf[s, t K + k, c .. c + 8]))
 __global__ __launch_bounds__(256) void moe_combine_kernel(
     const float* __restrict__ ybuf, short* __restrict__ out, long long n_vec, int h,
@@ -768,6 +1001,76 @@ torch::Tensor moe_ffn_fp8w(torch::Tensor x, torch::Tensor router_logits, torch::
                      dim3((unsigned)(h / 64), (unsigned)E, (unsigned)S), dim3(256), 0, stream,
                      (const short*)hbuf.data_ptr(), (const u8*)w_down8.data_ptr(),
                      (const u8*)nullptr, s_down.data_ptr<float>(), (const float*)nullptr, offs,
+                     pairs, topw, ybuf.data_ptr(), (int)f, (int)h, K, (int)P, cps);
+  const long long n_vec = T * (h / 8);
+  hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((n_vec + 255) / 256)), dim3(256), 0,
+                     stream, ybuf.data_ptr<float>(), (short*)out.data_ptr(), n_vec, (int)h, K,
+                     S, P);
+  return out;
+}
+
+// x bf16 [T, h], router_logits fp32 [T, E], c_gate/c_up uint8 [E, f, h / 2] with
+// e_gate/e_up uint8 [E, f, h / 32], c_down uint8 [E, h, f / 2] with e_down uint8
+// [E, h, f / 32] (MXFP4 codes and E8M0 scales) -> out bf16 [T, h]
+torch::Tensor moe_ffn_mxfp4w(torch::Tensor x, torch::Tensor router_logits, torch::Tensor c_gate,
+                             torch::Tensor e_gate, torch::Tensor c_up, torch::Tensor e_up,
+                             torch::Tensor c_down, torch::Tensor e_down, long top_k) {
+  check_router(router_logits, top_k);
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.dtype() == torch::kBFloat16 &&
+                  x.is_contiguous(),
+              "moe_ffn_mxfp4w: x must be contiguous bf16 [T, h] on the GPU");
+  const long long T = x.size(0), h = x.size(1), E = router_logits.size(1);
+  TORCH_CHECK(router_logits.size(0) == T, "moe_ffn_mxfp4w: router_logits must be [T, E]");
+  // codes [E, rows, cols / 2] or scales [E, rows, cols / 32]
+  auto bytes = [&](const torch::Tensor& w, long long rows, long long cols, int per) {
+    return w.is_cuda() && w.dim() == 3 && w.dtype() == torch::kUInt8 && w.is_contiguous() &&
+           w.size(0) == E && w.size(1) == rows && w.size(2) * per == cols;
+  };
+  TORCH_CHECK(c_gate.dim() == 3, "moe_ffn_mxfp4w: c_gate must be [E, f, h / 2]");
+  const long long f = c_gate.size(1);
+  TORCH_CHECK(bytes(c_gate, f, h, 2) && bytes(c_up, f, h, 2) && bytes(c_down, h, f, 2),
+              "moe_ffn_mxfp4w: the codes must be contiguous uint8 [E, f, h / 2], [E, f, h / 2] "
+              "and [E, h, f / 2] on the GPU");
+  TORCH_CHECK(bytes(e_gate, f, h, 32) && bytes(e_up, f, h, 32) && bytes(e_down, h, f, 32),
+              "moe_ffn_mxfp4w: the scales must be contiguous uint8 [E, f, h / 32], "
+              "[E, f, h / 32] and [E, h, f / 32] on the GPU");
+  TORCH_CHECK(h >= 128 && h % 128 == 0 && f >= 128 && f % 128 == 0 && h < (1 << 24) &&
+                  f < (1 << 24),
+              "moe_ffn_mxfp4w: h and f must be multiples of 128");
+  // h, f % 128 == 0 make every row of codes a multiple of 64 bytes and every
+  // row of scales a multiple of 4, so aligned bases keep all loads aligned
+  for (const torch::Tensor* t : {&x, &c_gate, &c_up, &c_down, &e_gate, &e_up, &e_down})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "moe_ffn_mxfp4w: operands must be 16-byte aligned");
+  auto out = torch::empty({T, h}, x.options());
+  if (T == 0) return out;
+
+  const int K = (int)top_k;
+  const long long P = T * K;
+  hipStream_t stream = hypha_stream();
+  Routing r = route(router_logits, K, stream);
+
+  const int nc_down = (int)((f + KC4 - 1) / KC4);
+  const int cps = down_chunks_per_split(nc_down, h, K, P);
+  const int S = (nc_down + cps - 1) / cps;
+
+  auto hbuf = torch::empty({P, f}, x.options());
+  auto ybuf = torch::empty({(long long)S, P, h}, x.options().dtype(torch::kFloat32));
+  const int* offs = r.offsets.data_ptr<int>();
+  const int* pairs = r.pairs.data_ptr<int>();
+  const float* topw = r.topw.data_ptr<float>();
+  using u8 = unsigned char;
+  constexpr int D = HYPHA_MOE_MXFP4_DEPTH;
+  hipLaunchKernelGGL((moe_expert_mxfp4w_kernel<false, D>),
+                     dim3((unsigned)(f / 32), (unsigned)E, 1), dim3(256), 0, stream,
+                     (const short*)x.data_ptr(), (const u8*)c_gate.data_ptr(),
+                     (const u8*)c_up.data_ptr(), (const u8*)e_gate.data_ptr(),
+                     (const u8*)e_up.data_ptr(), offs, pairs, topw, hbuf.data_ptr(), (int)h,
+                     (int)f, K, (int)P, (int)((h + KC4 - 1) / KC4));
+  hipLaunchKernelGGL((moe_expert_mxfp4w_kernel<true, D>),
+                     dim3((unsigned)(h / 64), (unsigned)E, (unsigned)S), dim3(256), 0, stream,
+                     (const short*)hbuf.data_ptr(), (const u8*)c_down.data_ptr(),
+                     (const u8*)nullptr, (const u8*)e_down.data_ptr(), (const u8*)nullptr, offs,
                      pairs, topw, ybuf.data_ptr(), (int)f, (int)h, K, (int)P, cps);
   const long long n_vec = T * (h / 8);
   hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((n_vec + 255) / 256)), dim3(256), 0,

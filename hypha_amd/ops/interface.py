@@ -30,6 +30,8 @@ The HIP extension ABI (hypha_amd._C):
   moe_ffn(x_bf16, router_logits_f32, w_gate, w_up, w_down, top_k) -> bf16 [T, h]
   moe_ffn_fp8w(x_bf16, router_logits_f32, w_gate8, s_gate, w_up8, s_up, w_down8, s_down,
                top_k) -> bf16 [T, h]
+  moe_ffn_mxfp4w(x_bf16, router_logits_f32, c_gate, e_gate, c_up, e_up, c_down, e_down,
+                 top_k) -> bf16 [T, h]
   moe_route(router_logits_f32, top_k) -> (topi_i32, topw_f32, offsets_i32, pairs_i32)
   linear_fp8w(x_bf16 [M, K], w8_e4m3 [N, K], scale_f32 [N]) -> bf16 [M, N]
   linear_mxfp4w(x_bf16 [M, K], codes_u8 [N, K / 2], scales_u8 [N, K / 32]) -> bf16 [M, N]
@@ -829,6 +831,55 @@ def moe_ffn_fp8w(x: torch.Tensor, router_logits: torch.Tensor, w_gate8: torch.Te
                                  w_down8.contiguous(), s_down.contiguous(), top_k)
     return reference.moe_ffn_fp8w(x, router_logits, w_gate8, s_gate, w_up8, s_up, w_down8,
                                   s_down, top_k)
+
+
+@torch.no_grad()
+def moe_ffn_mxfp4w(x: torch.Tensor, router_logits: torch.Tensor, c_gate: torch.Tensor,
+                   e_gate: torch.Tensor, c_up: torch.Tensor, e_up: torch.Tensor,
+                   c_down: torch.Tensor, e_down: torch.Tensor, top_k: int) -> torch.Tensor:
+    """ops.moe_ffn on weight-only MXFP4 experts: x bf16 [T, h], router_logits
+    fp32 [T, E], c_gate/c_up uint8 [E, f, h / 2] with e_gate/e_up uint8
+    [E, f, h / 32], c_down uint8 [E, h, f / 2] with e_down uint8 [E, h, f / 32]
+    -> bf16 [T, h]; the codes and E8M0 scales are what ops.quantize_mxfp4
+    returns for the 3-D weights, W' = ops.dequantize_mxfp4(codes, scales).
+    Routing as ops.moe_ffn; every W' value is a bf16 value, so the GEMMs run
+    on exact operands with fp32 accumulation, and the intermediate
+    silu(g) * u is rounded to bf16 once. On the GPU (moe_expert_mxfp4w_kernel
+    in ops/hip/moe_ffn.hip) only the chosen experts' codes and scales are
+    read, 4.25 bits per weight, converted and scaled in registers: no host
+    sync, launches sized by the shapes alone (safe to capture in a graph), no
+    float atomics (bit-reproducible). Native for the shapes of
+    moe_ffn_native_shapes; reference.moe_ffn_mxfp4w for every other shape and
+    for the CPU. No autograd."""
+    if x.dim() != 2 or router_logits.dim() != 2 or router_logits.shape[0] != x.shape[0]:
+        raise ValueError("moe_ffn_mxfp4w: x must be [T, h] and router_logits [T, E]")
+    t, h = x.shape
+    n_experts = router_logits.shape[1]
+    if (c_gate.dim() != 3 or c_gate.shape[0] != n_experts or 2 * c_gate.shape[2] != h
+            or h % 32 != 0):
+        raise ValueError("moe_ffn_mxfp4w: c_gate must be [E, f, h / 2] with h % 32 == 0")
+    f = c_gate.shape[1]
+    if f % 32 != 0 or c_up.shape != c_gate.shape or tuple(c_down.shape) != (n_experts, h, f // 2):
+        raise ValueError("moe_ffn_mxfp4w: c_up must be [E, f, h / 2] and c_down [E, h, f / 2] "
+                         "with f % 32 == 0")
+    if (tuple(e_gate.shape) != (n_experts, f, h // 32) or e_up.shape != e_gate.shape
+            or tuple(e_down.shape) != (n_experts, h, f // 32)):
+        raise ValueError("moe_ffn_mxfp4w: e_gate and e_up must be [E, f, h / 32] and e_down "
+                         "[E, h, f / 32]")
+    if (x.dtype != torch.bfloat16 or router_logits.dtype != torch.float32
+            or any(a.dtype != torch.uint8
+                   for a in (c_gate, e_gate, c_up, e_up, c_down, e_down))):
+        raise ValueError("moe_ffn_mxfp4w: x must be bf16, the codes and scales uint8, "
+                         "router_logits fp32")
+    if not isinstance(top_k, int) or not 1 <= top_k <= n_experts:
+        raise ValueError(f"moe_ffn_mxfp4w: top_k must be an int in [1, {n_experts}], got {top_k}")
+    if use_native(x) and moe_ffn_native_shapes(h, f, n_experts, top_k):
+        return _c().moe_ffn_mxfp4w(x.contiguous(), router_logits.contiguous(),
+                                   c_gate.contiguous(), e_gate.contiguous(),
+                                   c_up.contiguous(), e_up.contiguous(),
+                                   c_down.contiguous(), e_down.contiguous(), top_k)
+    return reference.moe_ffn_mxfp4w(x, router_logits, c_gate, e_gate, c_up, e_up, c_down,
+                                    e_down, top_k)
 
 
 # ---------------------------------------------------------------------------

@@ -28,7 +28,8 @@ temperature samples with torch.multinomial on the eager path. "kv_cache": "fp8" 
 weight-only e4m3 with per-row scales (models/fp8_linear.py), halving the
 weight bytes a decode step reads; "weight_quant": "mxfp4" quantises them to
 MXFP4 instead (models/mxfp4_linear.py: e2m1 codes with one power-of-two scale
-per 32 inputs, 4.25 bits per weight); any other value is an error.
+per 32 inputs, 4.25 bits per weight). Either one quantises the experts of the
+MoE family the same way; any other value is an error.
 
 "pad_token_id" makes every batch RAGGED: prompts are right-padded rows, a
 prompt's length is its row without the trailing run of that id (at least one

@@ -4,18 +4,25 @@ token count. Device events around `iters` forwards over 8 rotating inputs
 (so the routing varies), the two paths alternated `rounds` times; the median
 round and the spread are printed, one JSON line per T.
 
-  python tools/moe_ffn_bench.py [--iters 200] [--rounds 3] [--w-fp8]
-  rocprofv3 --kernel-trace --stats -- python tools/moe_ffn_bench.py --trace T [--w-fp8]
+  python tools/moe_ffn_bench.py [--iters 200] [--rounds 3] [--w-fp8 | --w-mxfp4]
+  rocprofv3 --kernel-trace --stats -- python tools/moe_ffn_bench.py --trace T [--w-fp8 | --w-mxfp4]
 
 --w-fp8 times three paths the same way: a copy of the module on weight-only
 fp8 experts (MoEMLP.quantize_experts_fp8_) through ops.moe_ffn_fp8w and
 through its fallback loop of ops.linear_fp8w, and the bf16 module's fused path
 as the baseline for time.
 
---trace T runs 40 fused forwards at T tokens (on the fp8 experts with --w-fp8)
+--w-mxfp4 does the same for a copy on weight-only MXFP4 experts
+(MoEMLP.quantize_experts_mxfp4_): ops.moe_ffn_mxfp4w, its fallback loop of
+ops.linear_mxfp4w, and the fp8 and bf16 fused paths as baselines, all four
+alternated in one call.
+
+--trace T runs 40 fused forwards at T tokens (on the fp8 experts with --w-fp8,
+on the MXFP4 experts with --w-mxfp4)
 and prints the number of live experts of each input, from which the bytes the
 two streaming kernels had to read follow (gate/up: live * 2 * f * h * B, down:
-live * h * f * B, B = 2 bytes per bf16 weight, 1 per fp8 code)."""
+live * h * f * B, B = 2 bytes per bf16 weight, 1 per fp8 code, 17 / 32 per
+MXFP4 weight: half a byte of code and 1 / 32 of a scale byte)."""
 import argparse
 import copy
 import json
@@ -29,7 +36,7 @@ from hypha_amd.models.moe import PRESETS, MoEMLP
 
 DEV = torch.device("cuda", 0)
 N_INPUTS = 8
-LIMITS = ("fused_ffn_max_tokens", "fused_ffn_fp8_max_tokens")
+LIMITS = ("fused_ffn_max_tokens", "fused_ffn_fp8_max_tokens", "fused_ffn_mxfp4_max_tokens")
 
 
 def build():
@@ -73,15 +80,19 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--trace", type=int, default=0)
     ap.add_argument("--w-fp8", action="store_true")
+    ap.add_argument("--w-mxfp4", action="store_true")
     args = ap.parse_args()
     mlp = build()
-    mlp8 = None
-    if args.w_fp8:
+    mlp8 = mlp4 = None
+    if args.w_fp8 or (args.w_mxfp4 and not args.trace):
         mlp8 = copy.deepcopy(mlp)  # its own cfg object too
         mlp8.quantize_experts_fp8_()
+    if args.w_mxfp4:
+        mlp4 = copy.deepcopy(mlp)
+        mlp4.quantize_experts_mxfp4_()
     if args.trace:
         xs = inputs(args.trace)
-        run = mlp8 if args.w_fp8 else mlp
+        run = mlp4 if args.w_mxfp4 else mlp8 if args.w_fp8 else mlp
         with torch.no_grad():
             live = [len(set(mlp.router(x[0]).float().topk(2, -1).indices.reshape(-1).tolist()))
                     for x in xs]
@@ -96,8 +107,11 @@ def main():
     paths = [("fused", mlp, True), ("loop", mlp, False)]
     if args.w_fp8:
         paths = [("fp8_fused", mlp8, True), ("fp8_loop", mlp8, False), ("bf16_fused", mlp, True)]
+    if args.w_mxfp4:
+        paths = [("mxfp4_fused", mlp4, True), ("mxfp4_loop", mlp4, False),
+                 ("fp8_fused", mlp8, True), ("bf16_fused", mlp, True)]
     token_counts = (1, 2, 4, 8, 16, 32, 64, 128, 256, 512)
-    if args.w_fp8:  # the fp8 loop dequantises whole experts above 128 rows: look further
+    if args.w_fp8 or args.w_mxfp4:  # the loops dequantise whole experts above 128 rows: look further
         token_counts += (1024, 2048, 4096)
     for t in token_counts:
         xs = inputs(t)
@@ -110,9 +124,12 @@ def main():
         for key, v in times.items():
             row[key + "_us"] = round(med(v), 1)
             row[key + "_min_max"] = [round(min(v), 1), round(max(v), 1)]
-        if args.w_fp8:  # the rule that sets fused_ffn_fp8_max_tokens
+        if args.w_fp8 and not args.w_mxfp4:  # the rule that sets fused_ffn_fp8_max_tokens
             row["fp8_fused_wins_every_round"] = all(
                 a < b for a, b in zip(times["fp8_fused"], times["fp8_loop"]))
+        if args.w_mxfp4:  # the rule that sets fused_ffn_mxfp4_max_tokens
+            row["mxfp4_fused_wins_every_round"] = all(
+                a < b for a, b in zip(times["mxfp4_fused"], times["mxfp4_loop"]))
         print(json.dumps(row), flush=True)
 
 
