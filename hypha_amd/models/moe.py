@@ -526,7 +526,8 @@ class MoEForCausalLM(nn.Module):
         into weight-only fp8 ones, in place and once (models/fp8_linear.py);
         it changes nothing on a model that is already quantised.
         weight_quant="mxfp4" does the same with MXFP4 linears and experts
-        (models/mxfp4_linear.py)."""
+        (models/mxfp4_linear.py); "mxfp4_a8" is "mxfp4" with the linears'
+        activations rounded to MXFP8 (the experts stay weight-only MXFP4)."""
         from .fp8_linear import check_weight_quant, quantize_linears_fp8_
         from .kv_cache import KVCache
         from .mxfp4_linear import quantize_linears_mxfp4_
@@ -534,8 +535,8 @@ class MoEForCausalLM(nn.Module):
         check_weight_quant(weight_quant)
         if weight_quant == "fp8":
             quantize_linears_fp8_(self)
-        elif weight_quant == "mxfp4":
-            quantize_linears_mxfp4_(self)
+        elif weight_quant in ("mxfp4", "mxfp4_a8"):
+            quantize_linears_mxfp4_(self, "mxfp8" if weight_quant == "mxfp4_a8" else None)
         if prefill_chunk is not None and prefill_chunk < 1:
             raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
         self.eval()

@@ -62,6 +62,7 @@ from .interface import (  # noqa: E402
     attn_prefill_paged,
     cross_entropy_loss,
     dequantize_mxfp4,
+    dequantize_mxfp8,
     extract_delta,
     flash_attention,
     fused_adamw,
@@ -80,6 +81,7 @@ from .interface import (  # noqa: E402
     moe_ffn_native_shapes,
     philox_uniform,
     quantize_mxfp4,
+    quantize_mxfp8,
     quantize_rows_e4m3,
     rmsnorm,
     sample_token,
@@ -116,6 +118,8 @@ __all__ = [
     "linear_mxfp4w_native_shapes",
     "quantize_mxfp4",
     "dequantize_mxfp4",
+    "quantize_mxfp8",
+    "dequantize_mxfp8",
     "extract_delta",
     "sample_token",
     "philox_uniform",

@@ -169,6 +169,10 @@ torch::Tensor moe_ffn_mxfp4w(torch::Tensor x, torch::Tensor router_logits, torch
 torch::Tensor linear_fp8w(torch::Tensor x, torch::Tensor w8, torch::Tensor scale);
 // linear_mxfp4w.hip (weight-only MXFP4 linear for decode-sized batches)
 torch::Tensor linear_mxfp4w(torch::Tensor x, torch::Tensor codes, torch::Tensor scales);
+// the same on activations quantised to MXFP8 (block-scaled MFMA); depth 0 = default
+torch::Tensor linear_mxfp4w_a8(torch::Tensor x, torch::Tensor codes, torch::Tensor scales,
+                               long depth);
+std::tuple<torch::Tensor, torch::Tensor> quantize_mxfp8(torch::Tensor x);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adamw_step_", &adamw_step_);
@@ -237,4 +241,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_ffn_mxfp4w", &moe_ffn_mxfp4w);
   m.def("linear_fp8w", &linear_fp8w);
   m.def("linear_mxfp4w", &linear_mxfp4w);
+  m.def("linear_mxfp4w_a8", &linear_mxfp4w_a8, pybind11::arg("x"), pybind11::arg("codes"),
+        pybind11::arg("scales"), pybind11::arg("depth") = 0);
+  m.def("quantize_mxfp8", &quantize_mxfp8);
 }

@@ -35,6 +35,8 @@ The HIP extension ABI (hypha_amd._C):
   moe_route(router_logits_f32, top_k) -> (topi_i32, topw_f32, offsets_i32, pairs_i32)
   linear_fp8w(x_bf16 [M, K], w8_e4m3 [N, K], scale_f32 [N]) -> bf16 [M, N]
   linear_mxfp4w(x_bf16 [M, K], codes_u8 [N, K / 2], scales_u8 [N, K / 32]) -> bf16 [M, N]
+  linear_mxfp4w_a8(x_bf16 [M, K], codes_u8, scales_u8, depth=0) -> bf16 [M, N]
+  quantize_mxfp8(x_bf16 [..., K]) -> (e4m3 [..., K], u8 [..., K / 32])
 """
 
 from __future__ import annotations
@@ -712,8 +714,27 @@ def linear_mxfp4w_native_shapes(n: int, k: int) -> bool:
 
 
 @torch.no_grad()
+def quantize_mxfp8(x: torch.Tensor):
+    """OCP MXFP8 of finite x [..., K], K % 32 == 0 -> (codes float8_e4m3fn
+    [..., K], scales uint8 [..., K / 32]): per block of 32 consecutive k the
+    E8M0 byte e + 127 with e = floor(log2(amax)) - 8 clamped to [-125, 125] (a
+    block of zeros takes -125) and the codes e4m3(clamp(x * 2^-e, -448, 448)),
+    ties to even; reference.quantize_mxfp8 states it in PyTorch. On the GPU,
+    contiguous bf16 x runs quantize_mxfp8_kernel (ops/hip/linear_mxfp4w.hip):
+    one launch sized by the shape, no atomics, the same bytes and values."""
+    if not x.is_floating_point() or x.dim() < 1 or x.shape[-1] % 32 != 0:
+        raise ValueError("quantize_mxfp8: x must be floating point [..., K] with K % 32 == 0")
+    if use_native(x) and x.dtype == torch.bfloat16 and x.is_contiguous() and x.numel() > 0:
+        return _c().quantize_mxfp8(x)
+    return reference.quantize_mxfp8(x)
+
+
+dequantize_mxfp8 = reference.dequantize_mxfp8
+
+
+@torch.no_grad()
 def linear_mxfp4w(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
-                  max_rows: int | None = None) -> torch.Tensor:
+                  max_rows: int | None = None, act_quant: str | None = None) -> torch.Tensor:
     """Linear layer on weight-only MXFP4 weights: x [..., K], codes uint8
     [N, K / 2] and scales uint8 [N, K / 32] as ops.quantize_mxfp4(W [N, K])
     produces them -> [..., N] in x's dtype, equal to x . W'^T with
@@ -725,7 +746,17 @@ def linear_mxfp4w(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
     linear_mxfp4w.hip): the codes are converted and scaled in registers by
     v_cvt_scalef32_pk_bf16_fp4, split-K is sized by the shapes alone (safe to
     capture in a graph), no float atomics (bit-reproducible). Every other case
-    takes reference.linear_mxfp4w (dequantise, then the library). No autograd."""
+    takes reference.linear_mxfp4w (dequantise, then the library). No autograd.
+
+    act_quant="mxfp8" is another numerical mode: x is first rounded to OCP
+    MXFP8 (ops.quantize_mxfp8: e4m3 with one E8M0 scale per 32 k), and the
+    result equals dequantize_mxfp8(quantize_mxfp8(x)) . W'^T. Under the same
+    conditions it runs linear_mxfp4w_a8_kernel, which feeds both sets of codes
+    and scale bytes to v_mfma_scale_f32_32x32x64_f8f6f4 as they are (a quantise
+    launch, the GEMM, the reduce if split); every other case takes
+    reference.linear_mxfp4w_a8. Any other act_quant raises ValueError."""
+    if act_quant not in (None, "mxfp8"):
+        raise ValueError(f"linear_mxfp4w: act_quant must be None or 'mxfp8', got {act_quant!r}")
     if codes.dim() != 2 or codes.dtype != torch.uint8:
         raise ValueError("linear_mxfp4w: codes must be uint8 [N, K / 2]")
     n, k = codes.shape[0], 2 * codes.shape[1]
@@ -738,10 +769,12 @@ def linear_mxfp4w(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
     m = x.numel() // k
     if (use_native(x) and x.dtype == torch.bfloat16 and 1 <= m <= max_rows
             and linear_mxfp4w_native_shapes(n, k)):
-        out = _c().linear_mxfp4w(x.reshape(m, k).contiguous(), codes.contiguous(),
-                                 scales.contiguous())
+        op = _c().linear_mxfp4w if act_quant is None else _c().linear_mxfp4w_a8
+        out = op(x.reshape(m, k).contiguous(), codes.contiguous(), scales.contiguous())
         return out.view(*x.shape[:-1], n)
-    return reference.linear_mxfp4w(x, codes, scales)
+    if act_quant is None:
+        return reference.linear_mxfp4w(x, codes, scales)
+    return reference.linear_mxfp4w_a8(x, codes, scales)
 
 
 # ---------------------------------------------------------------------------

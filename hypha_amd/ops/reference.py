@@ -213,6 +213,50 @@ def linear_mxfp4w(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) ->
     return x @ dequantize_mxfp4(codes, scales, x.dtype).t()
 
 
+@torch.no_grad()
+def quantize_mxfp8(x: torch.Tensor):
+    """OCP MXFP8 of finite x [..., K], K % 32 == 0 -> (codes float8_e4m3fn
+    [..., K], scales uint8 [..., K / 32]). Each block of 32 consecutive k shares
+    the power-of-two scale 2^e, e = floor(log2(amax)) - 8 clamped to
+    [-125, 125] (8 is e4m3's largest exponent; a block of zeros takes -125),
+    stored as the E8M0 byte e + 127. The code is x * 2^-e (exact in fp32 for
+    bf16 x), clamped to +-448 first, so that no cast decides the saturation,
+    then rounded to e4m3, ties to even."""
+    if not x.is_floating_point() or x.dim() < 1 or x.shape[-1] % 32 != 0:
+        raise ValueError("quantize_mxfp8: x must be floating point [..., K] with K % 32 == 0")
+    blocks = x.float().reshape(*x.shape[:-1], x.shape[-1] // 32, 32)
+    amax = blocks.abs().amax(-1)
+    # frexp: amax = m 2^ex with m in [0.5, 1), so floor(log2(amax)) = ex - 1
+    e = (torch.frexp(amax).exponent - 9).clamp(-125, 125)
+    e = torch.where(amax > 0, e, torch.full_like(e, -125))
+    q = (blocks * pow2_f32(-e).unsqueeze(-1)).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+    return q.reshape(x.shape), (e + 127).to(torch.uint8)
+
+
+@torch.no_grad()
+def dequantize_mxfp8(codes: torch.Tensor, scales: torch.Tensor,
+                     dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """The values of MXFP8 codes float8_e4m3fn [..., K] and E8M0 scales uint8
+    [..., K / 32] as quantize_mxfp8 produces them -> [..., K] in dtype:
+    e4m3(code) * 2^(scale - 127), exactly (every value is a bf16 value)."""
+    if (codes.dtype != torch.float8_e4m3fn or scales.dtype != torch.uint8 or codes.dim() < 1
+            or codes.shape[:-1] != scales.shape[:-1]
+            or codes.shape[-1] != 32 * scales.shape[-1]):
+        raise ValueError("dequantize_mxfp8: codes must be float8_e4m3fn [..., K] and scales "
+                         "uint8 [..., K / 32]")
+    vals = codes.float().reshape(*scales.shape, 32) * pow2_f32(
+        scales.to(torch.int32) - 127).unsqueeze(-1)
+    return vals.reshape(codes.shape).to(dtype)
+
+
+def linear_mxfp4w_a8(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """linear_mxfp4w on activations rounded to MXFP8 first: x goes through
+    quantize_mxfp8 and back (exactly, in x's dtype for bf16 and wider), then
+    meets the dequantised weights in the library's GEMM."""
+    xq = dequantize_mxfp8(*quantize_mxfp8(x), x.dtype)
+    return xq @ dequantize_mxfp4(codes, scales, x.dtype).t()
+
+
 def moe_ffn_fp8w(x: torch.Tensor, router_logits: torch.Tensor, w_gate8: torch.Tensor,
                  s_gate: torch.Tensor, w_up8: torch.Tensor, s_up: torch.Tensor,
                  w_down8: torch.Tensor, s_down: torch.Tensor, top_k: int) -> torch.Tensor:

@@ -45,6 +45,9 @@ def main():
     p.add_argument("--w-mxfp4", action="store_true",
                    help="weight-only MXFP4 linears (e2m1 codes + one E8M0 scale "
                         "per 32 inputs, ops.linear_mxfp4w)")
+    p.add_argument("--a-mxfp8", action="store_true",
+                   help="with --w-mxfp4: round the linears' activations to MXFP8 "
+                        "(act_quant='mxfp8', the block-scaled MFMA kernel)")
     p.add_argument("--ragged", metavar="LO:HI", default=None,
                    help="right-padded batch: prompt lengths drawn uniformly "
                         "from [LO, HI] (fixed seed, HI <= --prefill), generated "
@@ -59,6 +62,8 @@ def main():
         raise SystemExit("--paged needs --graph --ragged LO:HI")
     if args.w_fp8 and args.w_mxfp4:
         raise SystemExit("--w-fp8 and --w-mxfp4 exclude each other")
+    if args.a_mxfp8 and not args.w_mxfp4:
+        raise SystemExit("--a-mxfp8 needs --w-mxfp4")
 
     from hypha_amd import models
 
@@ -75,7 +80,7 @@ def main():
     if args.w_fp8:
         models.quantize_linears_fp8_(model)
     if args.w_mxfp4:
-        models.quantize_linears_mxfp4_(model)
+        models.quantize_linears_mxfp4_(model, "mxfp8" if args.a_mxfp8 else None)
     ids = torch.randint(0, model.cfg.vocab_size - 1, (args.batch, args.prefill),
                         device=dev)
 
@@ -115,7 +120,7 @@ def main():
 
         gen = functools.partial(model.generate, kv_quant=kvq)
 
-    tag = " w-fp8" if args.w_fp8 else " w-mxfp4" if args.w_mxfp4 else ""
+    tag = " w-fp8" if args.w_fp8 else " w-mxfp4-a8" if args.a_mxfp8 else " w-mxfp4" if args.w_mxfp4 else ""
     if args.sample is not None:
         import functools
 

@@ -14,7 +14,14 @@ in total (at most 64 copies), so that weights come from HBM. One JSON line per
 (shape, M): times in us, weight bytes (for MXFP4 codes plus scales) over time
 in TB/s, and the share of the peak HBM bandwidth (8 TB/s).
 
+--act mxfp8 adds the MXFP8-activation mode (act_quant="mxfp8"): "a8" is the
+whole op, quantise launch included, at the default prefetch depth; "a8_d1" and
+"a8_d2" are the same through the binding at depths 1 and 2; "quant" is the
+quantise launch alone, so a8 - quant is the GEMM (and reduce). a8_over_mxfp4w
+is the ratio of the times per round: median, min and max.
+
   python tools/linear_mxfp4w_bench.py [--graph] [--window 0.5] [--rounds 3] [--ms 1,8,32]
+                                      [--act mxfp8]
 """
 import argparse
 import json
@@ -105,6 +112,10 @@ def main():
     ap.add_argument("--graph", action="store_true",
                     help="time replays of a captured graph: kernel time without "
                          "host launch cost, as in the graphed decoder")
+    ap.add_argument("--act", choices=["mxfp8"], default=None,
+                    help="also time the MXFP8-activation mode (see above)")
+    ap.add_argument("--no-baselines", action="store_true",
+                    help="leave out the bf16 library and the fallback contenders")
     args = ap.parse_args()
     ops.native_available_or_raise()
     med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
@@ -119,7 +130,16 @@ def main():
                 "fp8w": lambda i: ops.linear_fp8w(x, ws[i][2], ws[i][3], max_rows=1 << 30),
                 "bf16": lambda i: x @ ws[i][4].t(),
             }
-            if name == "gate/up":
+            if args.act:
+                from hypha_amd import _C
+                contenders["a8"] = lambda i: ops.linear_mxfp4w(
+                    x, ws[i][0], ws[i][1], max_rows=1 << 30, act_quant="mxfp8")
+                contenders["a8_d1"] = lambda i: _C.linear_mxfp4w_a8(x, ws[i][0], ws[i][1], 1)
+                contenders["a8_d2"] = lambda i: _C.linear_mxfp4w_a8(x, ws[i][0], ws[i][1], 2)
+                contenders["quant"] = lambda i: ops.quantize_mxfp8(x)
+            if args.no_baselines:
+                del contenders["bf16"]
+            elif name == "gate/up":
                 contenders["fallback"] = lambda i: ops.linear_mxfp4w(x, ws[i][0], ws[i][1],
                                                                      max_rows=0)
             t = {c: [] for c in contenders}
@@ -131,7 +151,13 @@ def main():
             for c in contenders:
                 row[c + "_us"] = round(med(t[c]), 2)
                 row[c + "_min_max"] = [round(min(t[c]), 2), round(max(t[c]), 2)]
+            if args.act:
+                r = [a / b for a, b in zip(t["a8"], t["mxfp4w"])]
+                row["a8_over_mxfp4w"] = [round(v, 3) for v in (med(r), min(r), max(r))]
+                row["a8_TBps"] = round(nbytes["mxfp4w"] / med(t["a8"]) / 1e6, 3)
             for c, b in nbytes.items():
+                if c not in contenders:
+                    continue
                 row[c + "_TBps"] = round(b / med(t[c]) / 1e6, 3)
             row["mxfp4w_share_of_peak_hbm"] = round(
                 nbytes["mxfp4w"] / (med(t["mxfp4w"]) * 1e-6) / PEAK_HBM, 3)
