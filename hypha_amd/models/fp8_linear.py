@@ -72,6 +72,6 @@ def quantize_linears_fp8_(model: nn.Module) -> nn.Module:
 
 
 def check_weight_quant(weight_quant) -> None:
-    if weight_quant not in (None, "fp8", "mxfp4", "mxfp4_a8"):
-        raise ValueError("weight_quant must be None, 'fp8', 'mxfp4' or 'mxfp4_a8', "
-                         f"got {weight_quant!r}")
+    if weight_quant not in (None, "fp8", "mxfp4", "mxfp4_a8", "mxfp4_experts_a8"):
+        raise ValueError("weight_quant must be None, 'fp8', 'mxfp4', 'mxfp4_a8' or "
+                         f"'mxfp4_experts_a8', got {weight_quant!r}")

@@ -446,7 +446,9 @@ def _generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
     nothing on a model that is already quantised. weight_quant="mxfp4" does
     the same with MXFP4 linears (models/mxfp4_linear.py: 4.25 bits per
     weight); "mxfp4_a8" is "mxfp4" with the linears' activations rounded to
-    MXFP8 (act_quant="mxfp8": the block-scaled MFMA kernel)."""
+    MXFP8 (act_quant="mxfp8": the block-scaled MFMA kernel);
+    "mxfp4_experts_a8" is "mxfp4" with MXFP8 activations inside the expert FFN
+    of the MoE family only, so in this family it is "mxfp4"."""
     from .fp8_linear import check_weight_quant, quantize_linears_fp8_
     from .kv_cache import KVCache
     from .mxfp4_linear import quantize_linears_mxfp4_
@@ -454,8 +456,10 @@ def _generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
     check_weight_quant(weight_quant)
     if weight_quant == "fp8":
         quantize_linears_fp8_(self)
-    elif weight_quant in ("mxfp4", "mxfp4_a8"):
-        quantize_linears_mxfp4_(self, "mxfp8" if weight_quant == "mxfp4_a8" else None)
+    elif weight_quant in ("mxfp4", "mxfp4_a8", "mxfp4_experts_a8"):
+        quantize_linears_mxfp4_(
+            self, "mxfp8" if weight_quant == "mxfp4_a8" else None,
+            expert_act_quant="mxfp8" if weight_quant == "mxfp4_experts_a8" else None)
     check_sampler(sampler, temperature, top_p, seed)
     if prefill_chunk is not None and prefill_chunk < 1:
         raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")

@@ -134,6 +134,7 @@ class MoEMLP(nn.Module):
         for w in (self.w_gate, self.w_up, self.w_down):
             nn.init.normal_(w, std=cfg.init_std)
         self.ep = None  # (rank, size, group) after shard_experts_
+        self.act_quant = None  # ops.moe_ffn_mxfp4w's, set by quantize_experts_mxfp4_
 
     # buffers of a module with weight-only fp8 experts: codes [E, f, h],
     # [E, f, h], [E, h, f] and one fp32 scale per expert and weight row
@@ -174,12 +175,17 @@ class MoEMLP(nn.Module):
         return "c_gate" in self._buffers
 
     @torch.no_grad()
-    def quantize_experts_mxfp4_(self) -> "MoEMLP":
+    def quantize_experts_mxfp4_(self, act_quant: str | None = None) -> "MoEMLP":
         """Replace the three expert parameters by MXFP4 codes and E8M0 block
         scales (ops.quantize_mxfp4): 4.25 bits per weight against bf16's 16,
         served by ops.moe_ffn_mxfp4w at decode sizes and by ops.linear_mxfp4w
-        per expert above them. Inference only; a second call changes nothing.
-        Returns the module in eval mode."""
+        per expert above them. Inference only; a second call leaves the
+        weights as they are. act_quant is ops.moe_ffn_mxfp4w's and is set on
+        every call: None, or "mxfp8" to round the activations of both GEMM
+        stages to MXFP8 and take the block-scaled MFMA kernel. Returns the
+        module in eval mode."""
+        if act_quant not in (None, "mxfp8"):
+            raise ValueError(f"act_quant must be None or 'mxfp8', got {act_quant!r}")
         if self.ep is not None:
             raise ValueError("quantize_experts_mxfp4_: expert-parallel experts are not supported")
         if self.experts_fp8:
@@ -192,6 +198,7 @@ class MoEMLP(nn.Module):
                 del w
                 self.register_buffer(f"c_{name}", torch.stack([c for c, _ in q]))
                 self.register_buffer(f"e_{name}", torch.stack([s for _, s in q]))
+        self.act_quant = act_quant
         return self.eval()
 
     def _apply(self, fn, recurse=True):
@@ -232,7 +239,7 @@ class MoEMLP(nn.Module):
                 # the same device-routed path on 4.25 bits per weight
                 out = ops.moe_ffn_mxfp4w(xf.contiguous(), logits, self.c_gate, self.e_gate,
                                          self.c_up, self.e_up, self.c_down, self.e_down,
-                                         cfg.top_k)
+                                         cfg.top_k, act_quant=self.act_quant)
                 return out.reshape(b, s, h), xf.new_zeros(())
         elif self._use_fused_ffn(xf):
             # inference at decode sizes: routing, grouping and the expert
@@ -348,10 +355,12 @@ class MoEMLP(nn.Module):
                 he = ops.swiglu(ge, ue)
                 out_groups.append(ops.linear_fp8w(he, self.w_down8[e], self.s_down[e]))
             elif self.experts_mxfp4:
-                ge = ops.linear_mxfp4w(xe, self.c_gate[e], self.e_gate[e])
-                ue = ops.linear_mxfp4w(xe, self.c_up[e], self.e_up[e])
+                aq = self.act_quant
+                ge = ops.linear_mxfp4w(xe, self.c_gate[e], self.e_gate[e], act_quant=aq)
+                ue = ops.linear_mxfp4w(xe, self.c_up[e], self.e_up[e], act_quant=aq)
                 he = ops.swiglu(ge, ue)
-                out_groups.append(ops.linear_mxfp4w(he, self.c_down[e], self.e_down[e]))
+                out_groups.append(
+                    ops.linear_mxfp4w(he, self.c_down[e], self.e_down[e], act_quant=aq))
             else:
                 ge = xe @ self.w_gate[e].t()
                 ue = xe @ self.w_up[e].t()
@@ -527,7 +536,9 @@ class MoEForCausalLM(nn.Module):
         it changes nothing on a model that is already quantised.
         weight_quant="mxfp4" does the same with MXFP4 linears and experts
         (models/mxfp4_linear.py); "mxfp4_a8" is "mxfp4" with the linears'
-        activations rounded to MXFP8 (the experts stay weight-only MXFP4)."""
+        activations rounded to MXFP8 (the experts stay weight-only MXFP4);
+        "mxfp4_experts_a8" is "mxfp4" with MXFP8 activations inside the
+        expert FFN instead (the linears stay weight-only)."""
         from .fp8_linear import check_weight_quant, quantize_linears_fp8_
         from .kv_cache import KVCache
         from .mxfp4_linear import quantize_linears_mxfp4_
@@ -535,8 +546,10 @@ class MoEForCausalLM(nn.Module):
         check_weight_quant(weight_quant)
         if weight_quant == "fp8":
             quantize_linears_fp8_(self)
-        elif weight_quant in ("mxfp4", "mxfp4_a8"):
-            quantize_linears_mxfp4_(self, "mxfp8" if weight_quant == "mxfp4_a8" else None)
+        elif weight_quant in ("mxfp4", "mxfp4_a8", "mxfp4_experts_a8"):
+            quantize_linears_mxfp4_(
+                self, "mxfp8" if weight_quant == "mxfp4_a8" else None,
+                expert_act_quant="mxfp8" if weight_quant == "mxfp4_experts_a8" else None)
         if prefill_chunk is not None and prefill_chunk < 1:
             raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
         self.eval()

@@ -4,7 +4,9 @@ byte, with one E8M0 power-of-two scale per 32 consecutive inputs of a row
 against bf16's 16, and applied by ops.linear_mxfp4w: the weight-streaming HIP
 kernel for decode-sized batches, dequantise + library for prefill. The experts
 of the MoE family are quantised the same way by MoEMLP.quantize_experts_mxfp4_
-and applied by ops.moe_ffn_mxfp4w. Inference only."""
+and applied by ops.moe_ffn_mxfp4w. Both take an optional act_quant="mxfp8",
+which rounds their activations to MXFP8 and runs the block-scaled MFMA
+kernels. Inference only."""
 
 from __future__ import annotations
 
@@ -44,7 +46,8 @@ class Mxfp4Linear(nn.Module):
 
 
 @torch.no_grad()
-def quantize_linears_mxfp4_(model: nn.Module, act_quant: str | None = None) -> nn.Module:
+def quantize_linears_mxfp4_(model: nn.Module, act_quant: str | None = None,
+                            expert_act_quant: str | None = None) -> nn.Module:
     """Replace, in place, every bias-free nn.Linear whose shape
     ops/hip/linear_mxfp4w.hip serves by an Mxfp4Linear (in the Llama family:
     wq, wk, wv, wo, w_gate, w_up, w_down and an untied lm_head). A linear that
@@ -54,12 +57,16 @@ def quantize_linears_mxfp4_(model: nn.Module, act_quant: str | None = None) -> n
     quantised the same way (MoEMLP.quantize_experts_mxfp4_); its router is a
     linear like any other (with 8 outputs it is of another shape and stays
     bf16). act_quant is set on the linears created and on the Mxfp4Linears
-    already there; the experts stay weight-only. Returns the model in eval
-    mode."""
+    already there and leaves the experts weight-only; expert_act_quant is
+    the experts' own mode (MoEMLP.act_quant: "mxfp8" rounds the activations of
+    both stages of the expert FFN to MXFP8), set on every such MoEMLP, the
+    ones already quantised included. Returns the model in eval mode."""
     from .moe import MoEMLP
 
     if act_quant not in (None, "mxfp8"):
         raise ValueError(f"act_quant must be None or 'mxfp8', got {act_quant!r}")
+    if expert_act_quant not in (None, "mxfp8"):
+        raise ValueError(f"expert_act_quant must be None or 'mxfp8', got {expert_act_quant!r}")
 
     tied = {id(m.weight) for m in model.modules() if isinstance(m, nn.Embedding)}
     for parent in list(model.modules()):
@@ -73,5 +80,5 @@ def quantize_linears_mxfp4_(model: nn.Module, act_quant: str | None = None) -> n
         if isinstance(parent, MoEMLP) and ops.moe_ffn_native_shapes(
                 parent.cfg.hidden_size, parent.cfg.ffn_hidden, parent.cfg.n_experts,
                 parent.cfg.top_k):
-            parent.quantize_experts_mxfp4_()
+            parent.quantize_experts_mxfp4_(expert_act_quant)
     return model.eval()

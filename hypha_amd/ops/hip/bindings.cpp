@@ -165,6 +165,11 @@ torch::Tensor moe_ffn_fp8w(torch::Tensor x, torch::Tensor router_logits, torch::
 torch::Tensor moe_ffn_mxfp4w(torch::Tensor x, torch::Tensor router_logits, torch::Tensor c_gate,
                              torch::Tensor e_gate, torch::Tensor c_up, torch::Tensor e_up,
                              torch::Tensor c_down, torch::Tensor e_down, long top_k);
+// the same on activations quantised to MXFP8 (block-scaled MFMA); depth 0 = default
+torch::Tensor moe_ffn_mxfp4w_a8(torch::Tensor x, torch::Tensor router_logits,
+                                torch::Tensor c_gate, torch::Tensor e_gate, torch::Tensor c_up,
+                                torch::Tensor e_up, torch::Tensor c_down, torch::Tensor e_down,
+                                long top_k, long depth);
 // linear_fp8w.hip (weight-only e4m3 linear for decode-sized batches)
 torch::Tensor linear_fp8w(torch::Tensor x, torch::Tensor w8, torch::Tensor scale);
 // linear_mxfp4w.hip (weight-only MXFP4 linear for decode-sized batches)
@@ -239,6 +244,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_ffn", &moe_ffn);
   m.def("moe_ffn_fp8w", &moe_ffn_fp8w);
   m.def("moe_ffn_mxfp4w", &moe_ffn_mxfp4w);
+  m.def("moe_ffn_mxfp4w_a8", &moe_ffn_mxfp4w_a8, pybind11::arg("x"),
+        pybind11::arg("router_logits"), pybind11::arg("c_gate"), pybind11::arg("e_gate"),
+        pybind11::arg("c_up"), pybind11::arg("e_up"), pybind11::arg("c_down"),
+        pybind11::arg("e_down"), pybind11::arg("top_k"), pybind11::arg("depth") = 0);
   m.def("linear_fp8w", &linear_fp8w);
   m.def("linear_mxfp4w", &linear_mxfp4w);
   m.def("linear_mxfp4w_a8", &linear_mxfp4w_a8, pybind11::arg("x"), pybind11::arg("codes"),

@@ -76,6 +76,18 @@ __device__ __forceinline__ s16x8 e2m1x8_to_bf16x8(unsigned int d, float sc) {
   return __builtin_bit_cast(s16x8, v);
 }
 
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+
+// One v_mfma_scale_f32_32x32x64_f8f6f4. a: 32 e2m1 codes (cbsz 4), sa: their
+// E8M0 scale in byte SEL; b: 32 e4m3 codes (blgp 0), sb: their scale in byte SEL
+template <int SEL>
+__device__ __forceinline__ f32x16 mfma_e2m1_e4m3(u32x4 a, i32x8 b, f32x16 acc, unsigned int sa,
+                                                 unsigned int sb) {
+  const i32x8 a8 = {(int)a[0], (int)a[1], (int)a[2], (int)a[3], 0, 0, 0, 0};
+  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b, acc, 4, 0, SEL, (int)sa, SEL,
+                                                         (int)sb);
+}
+
 // Grid sizing for memory-bound grid-stride kernels: cap at ~8 blocks/CU.
 inline int elementwise_grid(long long n_items, int block = 256) {
   long long blocks = (n_items + block - 1) / block;

@@ -277,8 +277,6 @@ __global__ __launch_bounds__(256, 2) void linear_mxfp4w_kernel(
 
 // ---- MXFP8 activations --------------------------------------------------------
 
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-
 // x bf16 [n_vec * 8] -> q e4m3 [n_vec * 8], e E8M0 [n_vec / 4]; thread = 8
 // elements, quad = one block of 32. n_vec % 4 == 0: a quad is whole or absent.
 __global__ __launch_bounds__(256) void quantize_mxfp8_kernel(const short* __restrict__ x,
@@ -314,16 +312,6 @@ constexpr int XP = KC + 16;  // LDS row of a token: 512 e4m3 codes, then 16 scal
 #ifndef HYPHA_MXFP4W_A8_DEPTH
 #define HYPHA_MXFP4W_A8_DEPTH 1
 #endif
-
-// a: 32 e2m1 codes (cbsz 4), sa: their E8M0 scale in byte SEL; b: 32 e4m3
-// codes (blgp 0), sb: their scale in byte SEL
-template <int SEL>
-__device__ __forceinline__ f32x16 mfma_e2m1_e4m3(u32x4 a, i32x8 b, f32x16 acc, unsigned int sa,
-                                                 unsigned int sb) {
-  const i32x8 a8 = {(int)a[0], (int)a[1], (int)a[2], (int)a[3], 0, 0, 0, 0};
-  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b, acc, 4, 0, SEL, (int)sa, SEL,
-                                                         (int)sb);
-}
 
 // SPLIT as in linear_mxfp4w_kernel. xq e4m3 [M, K], xe E8M0 [M, K / 32].
 template <bool SPLIT, int DEPTH>

@@ -134,6 +134,43 @@
 //           loaded nor stored afterwards.
 //   LDS     66560 B, 2 waves/SIMD (__launch_bounds__(256, 2)); 218 / 216 VGPR
 //           (gate/up / down), 0 AGPR, 0 scratch.
+//
+// MXFP8 activations on those experts (moe_ffn_mxfp4w_a8): another numerical
+// mode. x and v = silu(g) * u are rounded to OCP MXFP8 (e4m3 codes, one E8M0
+// byte per 32 k of a row) and both GEMMs are v_mfma_scale_f32_32x32x64_f8f6f4
+// on the e2m1 and e4m3 codes and their scale bytes as loaded. Six launches:
+// route, group, quantize_mxfp8_kernel on x (once, for gate and up),
+// moe_expert_mxfp4w_a8_kernel<DOWN, DEPTH> twice, combine.
+// The kernel keeps moe_expert_mxfp4w_kernel's structure (early exit, weight
+// rows on M, 32 slots on N, 512-k chunks, waves 2 by k x 2 by row tile, one
+// code line per row, wave and chunk, branch-free loads DEPTH ahead, k-waves
+// met in LDS in wave order, the same split-K) with linear_mxfp4w_a8_kernel's
+// inner loop: a lane's load j is the A operand of one MFMA (cbsz 4), four
+// MFMAs a wave and chunk instead of sixteen and sixteen conversions.
+//   stage   a slot's row of a chunk is its 512 code bytes and then the chunk's
+//           16 scale bytes, pitch 528 B = 33 x 16 B: the sixteen lanes a
+//           128-bit LDS read serves together fall in sixteen different 16-byte
+//           columns (33 ln = ln mod 16), no conflict. 2 x 32 x 528 = 33792 B.
+//           Wave w stages the slots w + 4 i, i < 8: lane l loads bytes
+//           8 l .. + 8, so one load instruction is one whole row of one
+//           source row (pairs[..] / top_k of xq, pairs[..] of hq), which is
+//           wave-uniform and lives in SGPRs; lanes 0 - 31 also take one dword
+//           of the 16 scale bytes of slot w + 4 (l >> 2). Double-buffered, one
+//           barrier per chunk. A slot past the count holds zero codes under
+//           byte 0x7f (2^0), written once per token tile.
+//   v       after the meeting a workgroup of gate/up holds v in fp32 for 32 f
+//           rows x 32 slots, and rows0 % 32 == 0: one MX block per slot. The
+//           eight threads of a slot exchange the integer maximum of their
+//           magnitudes through 1 KiB of LDS behind the meeting image (no
+//           atomics), form the E8M0 byte from the fp32 exponent field and
+//           the codes by v_cvt_pk_fp8_f32 after a clamp to +-448
+//           (quantize_mxfp8's rule), and store 4 codes to hq [P, f] and, one
+//           thread in eight, the byte to he [P, f / 32]. Nothing is rounded to
+//           bf16 and the intermediate costs no launch.
+//   regs    DEPTH 2: 179 / 177 VGPR, 2 waves/SIMD; DEPTH 1: 141 / 137, 3
+//           waves/SIMD; 0 AGPR, 0 scratch. DEPTH 2 is the default: 7 % ahead
+//           at T = 1, 1 % from T = 256 on, 1 - 3 % behind at T = 8 and 64
+//           (profiles/moe_ffn_mxfp4w_a8.md, section 4).
 
 #include <torch/extension.h>
 
@@ -788,6 +825,243 @@ __global__ __launch_bounds__(256, 2) void moe_expert_mxfp4w_kernel(
   }
 }
 
+// ---- the same experts on MXFP8 activations: block-scaled MFMA -------------------
+
+constexpr int XPA = KC4 + 16;  // LDS row of a slot: 512 e4m3 codes, then the chunk's 16 scale bytes
+constexpr int XLA = NT / 4;  // slots a wave stages: one 8-byte load per lane is a slot's whole row
+static_assert(64 * 8 == KC4, "a wave's 8-byte loads must cover one row of a chunk");
+// chunks of codes and scale bytes a wave keeps in flight ahead of its MFMAs
+#ifndef HYPHA_MOE_MXFP4_A8_DEPTH
+#define HYPHA_MOE_MXFP4_A8_DEPTH 2
+#endif
+
+// moe_expert_mxfp4w_kernel on activations in OCP MXFP8 (e4m3 codes, one E8M0
+// byte per 32 k of a row); weights as there.
+// DOWN = false: actq/acte = codes [T, Kd] and scales [T, Kd / 32] of x, out =
+//               hq e4m3 [P, R] and oute = he E8M0 [P, R / 32]: silu(g) * u of
+//               the workgroup's 32 f rows, one MX block per slot, quantised
+//               from the fp32 accumulators.
+// DOWN = true : actq/acte = hq/he, out = ybuf fp32 [gridDim.z, P, R], oute unused.
+template <bool DOWN, int DEPTH>
+__global__ __launch_bounds__(256, 2) void moe_expert_mxfp4w_a8_kernel(
+    const unsigned char* __restrict__ actq, const unsigned char* __restrict__ acte,
+    const unsigned char* __restrict__ wa, const unsigned char* __restrict__ wb,
+    const unsigned char* __restrict__ sa, const unsigned char* __restrict__ sb,
+    const int* __restrict__ offsets, const int* __restrict__ pairs,
+    const float* __restrict__ topw, void* __restrict__ outp, unsigned char* __restrict__ oute,
+    int Kd, int R, int top_k, int P, int cps) {
+  static_assert(DEPTH >= 1 && DEPTH <= 3, "prefetch depth");
+  constexpr int NS = DEPTH + 1;  // register sets: the chunk in use and DEPTH in flight
+  const int e = blockIdx.y;
+  const int off = offsets[e];
+  const int cnt = offsets[e + 1] - off;
+  if (cnt == 0) return;  // nobody chose this expert: no weight is read
+
+  __shared__ __attribute__((aligned(16))) unsigned char xs[2 * NT * XPA];
+  float* red = reinterpret_cast<float*>(xs);  // [4 waves][16][64] after the k loop
+  // behind it, the block's amax by thread: [8 row groups][32 slots]
+  unsigned int* amx = reinterpret_cast<unsigned int*>(xs) + 4 * 16 * 64;
+  static_assert((4 * 16 * 64 + 8 * 32) * sizeof(float) <= 2 * NT * XPA,
+                "reduction image must fit the staging buffers");
+
+  const int tid = threadIdx.x;
+  // the wave index through readfirstlane: what follows from it (k half, row
+  // tile, the staged slots' source rows, the chunk offsets) lives in SGPRs
+  const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ln = lane & 31, hi = lane >> 5;
+  const int kw = w & 1, rt = w >> 1;  // this wave's k half of a chunk and its row tile
+  const int rows0 = blockIdx.x * (DOWN ? 64 : 32);
+  const int nb = Kd / 32;  // scale bytes of a row
+  // a wave-uniform 64-bit base plus a 32-bit lane offset that never changes
+  const long long row0 = (long long)e * R + rows0 + (DOWN ? 32 * rt : 0);
+  const unsigned char* ap = ((DOWN || rt == 0) ? wa : wb) + row0 * (Kd / 2);
+  const unsigned char* sp = ((DOWN || rt == 0) ? sa : sb) + row0 * nb;
+  const unsigned int aoff = (unsigned int)ln * (unsigned int)(Kd / 2) + 16 * hi;
+  const unsigned int soff = (unsigned int)ln * nb;
+  const int nc = (Kd + KC4 - 1) / KC4;
+  const int c0 = blockIdx.z * cps;
+  const int c1 = min(nc, c0 + cps);
+  // staging: wave w takes the slots w + 4 i, i < 8, lane l the code bytes
+  // 8 l .. + 8 of the chunk, so a load is one whole 512-byte row of one source
+  // row; the lower half-wave also takes dword ln & 3 of the 16 scale bytes of
+  // slot w + 4 (ln >> 2)
+  const int xb = 8 * lane;
+  const int eslot = w + 4 * (ln >> 2), eb = 4 * (ln & 3);
+
+  for (int t0 = 0; t0 < cnt; t0 += NT) {
+    // source row of each slot this wave stages (wave-uniform), -1 past the
+    // count: such a slot gets zero codes under the scale 0x7f (2^0) in both
+    // buffers here and is neither loaded into nor stored again
+    int rowi[XLA];
+#pragma unroll
+    for (int i = 0; i < XLA; ++i) {
+      const int s = t0 + w + 4 * i;
+      rowi[i] = -1;
+      if (s < cnt) {
+        rowi[i] = DOWN ? pairs[off + s] : pairs[off + s] / top_k;
+      } else {
+        *reinterpret_cast<u32x2*>(xs + (w + 4 * i) * XPA + xb) = u32x2{};
+        *reinterpret_cast<u32x2*>(xs + (NT + w + 4 * i) * XPA + xb) = u32x2{};
+      }
+    }
+    int erowi = -1;  // source row of this lane's scale dword
+    if (hi == 0) {
+      if (t0 + eslot < cnt) {
+        erowi = DOWN ? pairs[off + t0 + eslot] : pairs[off + t0 + eslot] / top_k;
+      } else {
+        *reinterpret_cast<unsigned int*>(xs + eslot * XPA + KC4 + eb) = 0x7f7f7f7fu;
+        *reinterpret_cast<unsigned int*>(xs + (NT + eslot) * XPA + KC4 + eb) = 0x7f7f7f7fu;
+      }
+    }
+    // The activation loads carry no branch either. A dead slot or a chunk at
+    // or past c1 reads row 0 instead, a lane whose bytes lie past Kd (the last
+    // chunk of a Kd that is no multiple of KC4) the first bytes of its chunk:
+    // every such address is inside the tensor. A dead slot is never stored;
+    // what a live slot stores past Kd is never read, because the MFMAs at that
+    // k are skipped.
+    auto load_x = [&](int c, u32x2(&xr)[XLA], unsigned int& er) {
+      const unsigned int lo = c * KC4 + xb < Kd ? xb : 0;
+#pragma unroll
+      for (int i = 0; i < XLA; ++i) {
+        const long long ro =
+            (c < c1 && rowi[i] >= 0) ? (long long)rowi[i] * Kd + c * KC4 : 0;  // wave-uniform
+        xr[i] = *reinterpret_cast<const u32x2*>(actq + ro + lo);
+      }
+      const bool in = c < c1 && erowi >= 0 && c * (KC4 / 32) + eb < nb;
+      er = *reinterpret_cast<const unsigned int*>(
+          acte + (in ? (long long)erowi * nb + c * (KC4 / 32) + eb : 0));
+    };
+    auto store_x = [&](int buf, const u32x2(&xr)[XLA], unsigned int er) {
+#pragma unroll
+      for (int i = 0; i < XLA; ++i)
+        if (rowi[i] >= 0)
+          *reinterpret_cast<u32x2*>(xs + (buf * NT + w + 4 * i) * XPA + xb) = xr[i];
+      if (erowi >= 0)
+        *reinterpret_cast<unsigned int*>(xs + (buf * NT + eslot) * XPA + KC4 + eb) = er;
+    };
+    // this wave's 256 k of chunk c without a branch, as in moe_expert_mxfp4w_kernel
+    auto load_w = [&](int c, u32x4(&wr)[4], unsigned int(&sr)[2]) {
+      const int k = c * KC4 + kw * KW4;
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        const bool in = c < c1 && k + 128 * g < Kd;  // wave-uniform
+        const long long oc = in ? (long long)c * (KC4 / 2) + kw * (KW4 / 2) + 64 * g : 0;
+        const long long os = in ? (long long)c * (KC4 / 32) + kw * (KW4 / 32) + 4 * g : 0;
+        wr[2 * g] = *reinterpret_cast<const u32x4*>(ap + oc + aoff);
+        wr[2 * g + 1] = *reinterpret_cast<const u32x4*>(ap + (oc + 32) + aoff);
+        sr[g] = *reinterpret_cast<const unsigned int*>(sp + os + soff);
+      }
+    };
+
+    f32x16 acc = {};
+    // set s holds chunk c0 + s, c0 + s + NS, ...: the loop below is unrolled
+    // over the sets, so every index is a constant and nothing is ever copied
+    u32x4 wr[NS][4] = {};
+    unsigned int sr[NS][2] = {};
+    u32x2 xr[XLA];
+    unsigned int er;
+    load_x(c0, xr, er);
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d) load_w(c0 + d, wr[d], sr[d]);
+    store_x(0, xr, er);
+    __syncthreads();
+    for (int cb = c0; cb < c1; cb += NS) {
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const int c = cb + s;
+        if (c < c1) {  // uniform over the workgroup
+          const int buf = (c - c0) & 1;
+          const bool more = c + 1 < c1;
+          load_x(c + 1, xr, er);
+          load_w(c + DEPTH, wr[(s + DEPTH) % NS], sr[(s + DEPTH) % NS]);
+          const int k = c * KC4 + kw * KW4;
+          // lane (ln, hi) of step j: A is load j as it came (32 e2m1 codes,
+          // k = 64 j + 32 hi .. + 32, scale byte 2 j + hi of the wave's 8); B
+          // is slot ln's e4m3 bytes at 64 j + 16 hi and 64 j + 32 + 16 hi, its
+          // scale byte 2 j + hi of the slot's 8 (linear_mxfp4w_a8_kernel's map)
+          const unsigned char* trow = xs + (buf * NT + ln) * XPA;
+          const unsigned char* bp = trow + kw * KW4 + 16 * hi;
+          const u32x2 sbv = *reinterpret_cast<const u32x2*>(trow + KC4 + kw * (KW4 / 32));
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (k + 64 * j < Kd) {
+              const u32x4 b0 = *reinterpret_cast<const u32x4*>(bp + 64 * j);
+              const u32x4 b1 = *reinterpret_cast<const u32x4*>(bp + 64 * j + 32);
+              const i32x8 b = {(int)b0[0], (int)b0[1], (int)b0[2], (int)b0[3],
+                               (int)b1[0], (int)b1[1], (int)b1[2], (int)b1[3]};
+              const unsigned int sw = sr[s][j >> 1] >> (8 * hi), sx = sbv[j >> 1] >> (8 * hi);
+              acc = (j & 1) ? mfma_e2m1_e4m3<2>(wr[s][j], b, acc, sw, sx)
+                            : mfma_e2m1_e4m3<0>(wr[s][j], b, acc, sw, sx);
+            }
+          }
+          if (more) store_x(buf ^ 1, xr, er);
+          __syncthreads();
+        }
+      }
+    }
+
+    // the two k-waves of each tile meet in LDS and are added in wave order
+#pragma unroll
+    for (int r = 0; r < 16; ++r) red[(w * 16 + r) * 64 + lane] = acc[r];
+    __syncthreads();
+    // thread (n, q): slot n, tile rows 4 q .. + 4, which are registers
+    // 4 (q >> 1) .. + 4 of MFMA lane 32 (q & 1) + n
+    const int n = tid & 31, q = tid >> 5;
+    f32x4 s0, s1;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = 4 * (q >> 1) + i, src = 32 * (q & 1) + n;
+      s0[i] = red[(0 * 16 + r) * 64 + src] + red[(1 * 16 + r) * 64 + src];
+      s1[i] = red[(2 * 16 + r) * 64 + src] + red[(3 * 16 + r) * 64 + src];
+    }
+    const bool live = t0 + n < cnt;
+    const int p = live ? pairs[off + t0 + n] : 0;
+    if (!DOWN) {
+      // s0 = gate, s1 = up. The tile's 32 f rows are one MX block of the down
+      // projection's k: quantize_mxfp8's rule on the fp32 values. The eight
+      // threads of a slot exchange their largest magnitude (finite fp32
+      // magnitudes order as their bits do) through LDS.
+      float v[4];
+      unsigned int am = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        v[i] = s0[i] / (1.f + __expf(-s0[i])) * s1[i];
+        am = max(am, __float_as_uint(v[i]) & 0x7fffffffu);
+      }
+      amx[q * 32 + n] = am;
+      __syncthreads();
+#pragma unroll
+      for (int qq = 0; qq < 8; ++qq) am = max(am, amx[qq * 32 + n]);
+      // e = floor(log2(amax)) - 8 clamped below at -125 (zeros and fp32
+      // denormals included); an fp32 exponent cannot reach the upper clamp
+      const int byte = max(2, (int)(am >> 23) - 8);
+      // 2^(127 - byte): field 254 - byte in [8, 252], a normal fp32
+      const float inv = __uint_as_float((unsigned int)(254 - byte) << 23);
+      if (live) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = fminf(fmaxf(v[i] * inv, -448.f), 448.f);
+        int d = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
+        d = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], d, true);
+        *reinterpret_cast<int*>(static_cast<unsigned char*>(outp) + (long long)p * R + rows0 +
+                                4 * q) = d;
+        if (q == 0) oute[(long long)p * (R / 32) + rows0 / 32] = (unsigned char)byte;
+      }
+    } else if (live) {
+      const float wt = topw[p];
+      float* y = static_cast<float*>(outp) + ((long long)blockIdx.z * P + p) * R + rows0 + 4 * q;
+      f32x4 y0, y1;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        y0[i] = s0[i] * wt;
+        y1[i] = s1[i] * wt;
+      }
+      *reinterpret_cast<f32x4*>(y) = y0;
+      *reinterpret_cast<f32x4*>(y + 32) = y1;
+    }
+    __syncthreads();  // red aliases the next token tile's staging buffers
+  }
+}
+
 // out[t, c .. c + 8] = bf16(sum_k (sum_s ybuf[s, t K + k, c .. c + 8]))
 __global__ __launch_bounds__(256) void moe_combine_kernel(
     const float* __restrict__ ybuf, short* __restrict__ out, long long n_vec, int h,
@@ -866,7 +1140,86 @@ int down_chunks_per_split(int nc, long long h, int K, long long P) {
   return (nc + want - 1) / want;
 }
 
+// The operand checks of moe_ffn_mxfp4w and moe_ffn_mxfp4w_a8. -> f
+long long check_mxfp4_experts(const char* op, const torch::Tensor& x,
+                              const torch::Tensor& router_logits, const torch::Tensor& c_gate,
+                              const torch::Tensor& e_gate, const torch::Tensor& c_up,
+                              const torch::Tensor& e_up, const torch::Tensor& c_down,
+                              const torch::Tensor& e_down, long top_k) {
+  check_router(router_logits, top_k);
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.dtype() == torch::kBFloat16 &&
+                  x.is_contiguous(),
+              op, ": x must be contiguous bf16 [T, h] on the GPU");
+  const long long T = x.size(0), h = x.size(1), E = router_logits.size(1);
+  TORCH_CHECK(router_logits.size(0) == T, op, ": router_logits must be [T, E]");
+  // codes [E, rows, cols / 2] or scales [E, rows, cols / 32]
+  auto bytes = [&](const torch::Tensor& w, long long rows, long long cols, int per) {
+    return w.is_cuda() && w.dim() == 3 && w.dtype() == torch::kUInt8 && w.is_contiguous() &&
+           w.size(0) == E && w.size(1) == rows && w.size(2) * per == cols;
+  };
+  TORCH_CHECK(c_gate.dim() == 3, op, ": c_gate must be [E, f, h / 2]");
+  const long long f = c_gate.size(1);
+  TORCH_CHECK(bytes(c_gate, f, h, 2) && bytes(c_up, f, h, 2) && bytes(c_down, h, f, 2), op,
+              ": the codes must be contiguous uint8 [E, f, h / 2], [E, f, h / 2] and "
+              "[E, h, f / 2] on the GPU");
+  TORCH_CHECK(bytes(e_gate, f, h, 32) && bytes(e_up, f, h, 32) && bytes(e_down, h, f, 32), op,
+              ": the scales must be contiguous uint8 [E, f, h / 32], [E, f, h / 32] and "
+              "[E, h, f / 32] on the GPU");
+  TORCH_CHECK(h >= 128 && h % 128 == 0 && f >= 128 && f % 128 == 0 && h < (1 << 24) &&
+                  f < (1 << 24),
+              op, ": h and f must be multiples of 128");
+  // h, f % 128 == 0 make every row of codes a multiple of 64 bytes and every
+  // row of scales a multiple of 4, so aligned bases keep all loads aligned
+  for (const torch::Tensor* t : {&x, &c_gate, &c_up, &c_down, &e_gate, &e_up, &e_down})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, op,
+                ": operands must be 16-byte aligned");
+  return f;
+}
+
+// gate/up, down and combine of moe_ffn_mxfp4w_a8 at one prefetch depth
+template <int D>
+void launch_experts_a8(const torch::Tensor& xq, const torch::Tensor& xe, const Routing& r,
+                       const torch::Tensor& c_gate, const torch::Tensor& e_gate,
+                       const torch::Tensor& c_up, const torch::Tensor& e_up,
+                       const torch::Tensor& c_down, const torch::Tensor& e_down,
+                       torch::Tensor& out, int K, hipStream_t stream) {
+  const long long T = out.size(0), h = out.size(1), E = c_gate.size(0), f = c_gate.size(1);
+  const long long P = T * K;
+  const int nc_down = (int)((f + KC4 - 1) / KC4);
+  const int cps = down_chunks_per_split(nc_down, h, K, P);
+  const int S = (nc_down + cps - 1) / cps;
+
+  const auto u8opt = out.options().dtype(torch::kUInt8);
+  auto hq = torch::empty({P, f}, u8opt);       // e4m3 codes of silu(g) * u
+  auto he = torch::empty({P, f / 32}, u8opt);  // their E8M0 scales
+  auto ybuf = torch::empty({(long long)S, P, h}, out.options().dtype(torch::kFloat32));
+  const int* offs = r.offsets.data_ptr<int>();
+  const int* pairs = r.pairs.data_ptr<int>();
+  const float* topw = r.topw.data_ptr<float>();
+  using u8 = unsigned char;
+  hipLaunchKernelGGL((moe_expert_mxfp4w_a8_kernel<false, D>),
+                     dim3((unsigned)(f / 32), (unsigned)E, 1), dim3(256), 0, stream,
+                     (const u8*)xq.data_ptr(), (const u8*)xe.data_ptr(),
+                     (const u8*)c_gate.data_ptr(), (const u8*)c_up.data_ptr(),
+                     (const u8*)e_gate.data_ptr(), (const u8*)e_up.data_ptr(), offs, pairs, topw,
+                     hq.data_ptr(), (u8*)he.data_ptr(), (int)h, (int)f, K, (int)P,
+                     (int)((h + KC4 - 1) / KC4));
+  hipLaunchKernelGGL((moe_expert_mxfp4w_a8_kernel<true, D>),
+                     dim3((unsigned)(h / 64), (unsigned)E, (unsigned)S), dim3(256), 0, stream,
+                     (const u8*)hq.data_ptr(), (const u8*)he.data_ptr(),
+                     (const u8*)c_down.data_ptr(), (const u8*)nullptr,
+                     (const u8*)e_down.data_ptr(), (const u8*)nullptr, offs, pairs, topw,
+                     ybuf.data_ptr(), (u8*)nullptr, (int)f, (int)h, K, (int)P, cps);
+  const long long n_vec = T * (h / 8);
+  hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((n_vec + 255) / 256)), dim3(256), 0,
+                     stream, ybuf.data_ptr<float>(), (short*)out.data_ptr(), n_vec, (int)h, K,
+                     S, P);
+}
+
 }  // namespace
+
+// linear_mxfp4w.hip: bf16 [..., K] -> (e4m3 codes [..., K], E8M0 scales [..., K / 32])
+std::tuple<torch::Tensor, torch::Tensor> quantize_mxfp8(torch::Tensor x);
 
 // router_logits fp32 [T, E] -> (topi int32 [T, K], topw fp32 [T, K],
 // offsets int32 [E + 1], pairs int32 [T * K])
@@ -1015,33 +1368,9 @@ torch::Tensor moe_ffn_fp8w(torch::Tensor x, torch::Tensor router_logits, torch::
 torch::Tensor moe_ffn_mxfp4w(torch::Tensor x, torch::Tensor router_logits, torch::Tensor c_gate,
                              torch::Tensor e_gate, torch::Tensor c_up, torch::Tensor e_up,
                              torch::Tensor c_down, torch::Tensor e_down, long top_k) {
-  check_router(router_logits, top_k);
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.dtype() == torch::kBFloat16 &&
-                  x.is_contiguous(),
-              "moe_ffn_mxfp4w: x must be contiguous bf16 [T, h] on the GPU");
+  const long long f = check_mxfp4_experts("moe_ffn_mxfp4w", x, router_logits, c_gate, e_gate,
+                                          c_up, e_up, c_down, e_down, top_k);
   const long long T = x.size(0), h = x.size(1), E = router_logits.size(1);
-  TORCH_CHECK(router_logits.size(0) == T, "moe_ffn_mxfp4w: router_logits must be [T, E]");
-  // codes [E, rows, cols / 2] or scales [E, rows, cols / 32]
-  auto bytes = [&](const torch::Tensor& w, long long rows, long long cols, int per) {
-    return w.is_cuda() && w.dim() == 3 && w.dtype() == torch::kUInt8 && w.is_contiguous() &&
-           w.size(0) == E && w.size(1) == rows && w.size(2) * per == cols;
-  };
-  TORCH_CHECK(c_gate.dim() == 3, "moe_ffn_mxfp4w: c_gate must be [E, f, h / 2]");
-  const long long f = c_gate.size(1);
-  TORCH_CHECK(bytes(c_gate, f, h, 2) && bytes(c_up, f, h, 2) && bytes(c_down, h, f, 2),
-              "moe_ffn_mxfp4w: the codes must be contiguous uint8 [E, f, h / 2], [E, f, h / 2] "
-              "and [E, h, f / 2] on the GPU");
-  TORCH_CHECK(bytes(e_gate, f, h, 32) && bytes(e_up, f, h, 32) && bytes(e_down, h, f, 32),
-              "moe_ffn_mxfp4w: the scales must be contiguous uint8 [E, f, h / 32], "
-              "[E, f, h / 32] and [E, h, f / 32] on the GPU");
-  TORCH_CHECK(h >= 128 && h % 128 == 0 && f >= 128 && f % 128 == 0 && h < (1 << 24) &&
-                  f < (1 << 24),
-              "moe_ffn_mxfp4w: h and f must be multiples of 128");
-  // h, f % 128 == 0 make every row of codes a multiple of 64 bytes and every
-  // row of scales a multiple of 4, so aligned bases keep all loads aligned
-  for (const torch::Tensor* t : {&x, &c_gate, &c_up, &c_down, &e_gate, &e_up, &e_down})
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
-                "moe_ffn_mxfp4w: operands must be 16-byte aligned");
   auto out = torch::empty({T, h}, x.options());
   if (T == 0) return out;
 
@@ -1076,5 +1405,33 @@ torch::Tensor moe_ffn_mxfp4w(torch::Tensor x, torch::Tensor router_logits, torch
   hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((n_vec + 255) / 256)), dim3(256), 0,
                      stream, ybuf.data_ptr<float>(), (short*)out.data_ptr(), n_vec, (int)h, K,
                      S, P);
+  return out;
+}
+
+// moe_ffn_mxfp4w on activations rounded to OCP MXFP8: x is quantised once for
+// gate and up, silu(g) * u in the gate/up epilogue, and both GEMMs are
+// block-scaled MFMAs on the codes as loaded. Route, group, quantise, gate/up,
+// down, combine: every launch sized by (T, E, h, f, top_k) alone.
+// depth: chunks of weights in flight per wave, 0 = the default (for measuring)
+torch::Tensor moe_ffn_mxfp4w_a8(torch::Tensor x, torch::Tensor router_logits,
+                                torch::Tensor c_gate, torch::Tensor e_gate, torch::Tensor c_up,
+                                torch::Tensor e_up, torch::Tensor c_down, torch::Tensor e_down,
+                                long top_k, long depth) {
+  check_mxfp4_experts("moe_ffn_mxfp4w_a8", x, router_logits, c_gate, e_gate, c_up, e_up, c_down,
+                      e_down, top_k);
+  TORCH_CHECK(depth >= 0 && depth <= 2, "moe_ffn_mxfp4w_a8: depth must be 0, 1 or 2");
+  auto out = torch::empty(x.sizes(), x.options());
+  if (x.size(0) == 0) return out;
+
+  hipStream_t stream = hypha_stream();
+  Routing r = route(router_logits, (int)top_k, stream);
+  auto [xq, xe] = quantize_mxfp8(x);
+  if (depth == 0) depth = HYPHA_MOE_MXFP4_A8_DEPTH;
+  if (depth == 1)
+    launch_experts_a8<1>(xq, xe, r, c_gate, e_gate, c_up, e_up, c_down, e_down, out, (int)top_k,
+                         stream);
+  else
+    launch_experts_a8<2>(xq, xe, r, c_gate, e_gate, c_up, e_up, c_down, e_down, out, (int)top_k,
+                         stream);
   return out;
 }

@@ -32,6 +32,7 @@ The HIP extension ABI (hypha_amd._C):
                top_k) -> bf16 [T, h]
   moe_ffn_mxfp4w(x_bf16, router_logits_f32, c_gate, e_gate, c_up, e_up, c_down, e_down,
                  top_k) -> bf16 [T, h]
+  moe_ffn_mxfp4w_a8(the same operands, top_k, depth=0) -> bf16 [T, h]
   moe_route(router_logits_f32, top_k) -> (topi_i32, topw_f32, offsets_i32, pairs_i32)
   linear_fp8w(x_bf16 [M, K], w8_e4m3 [N, K], scale_f32 [N]) -> bf16 [M, N]
   linear_mxfp4w(x_bf16 [M, K], codes_u8 [N, K / 2], scales_u8 [N, K / 32]) -> bf16 [M, N]
@@ -869,7 +870,8 @@ def moe_ffn_fp8w(x: torch.Tensor, router_logits: torch.Tensor, w_gate8: torch.Te
 @torch.no_grad()
 def moe_ffn_mxfp4w(x: torch.Tensor, router_logits: torch.Tensor, c_gate: torch.Tensor,
                    e_gate: torch.Tensor, c_up: torch.Tensor, e_up: torch.Tensor,
-                   c_down: torch.Tensor, e_down: torch.Tensor, top_k: int) -> torch.Tensor:
+                   c_down: torch.Tensor, e_down: torch.Tensor, top_k: int,
+                   act_quant: str | None = None) -> torch.Tensor:
     """ops.moe_ffn on weight-only MXFP4 experts: x bf16 [T, h], router_logits
     fp32 [T, E], c_gate/c_up uint8 [E, f, h / 2] with e_gate/e_up uint8
     [E, f, h / 32], c_down uint8 [E, h, f / 2] with e_down uint8 [E, h, f / 32]
@@ -883,7 +885,19 @@ def moe_ffn_mxfp4w(x: torch.Tensor, router_logits: torch.Tensor, c_gate: torch.T
     sync, launches sized by the shapes alone (safe to capture in a graph), no
     float atomics (bit-reproducible). Native for the shapes of
     moe_ffn_native_shapes; reference.moe_ffn_mxfp4w for every other shape and
-    for the CPU. No autograd."""
+    for the CPU. No autograd.
+
+    act_quant="mxfp8" is another numerical mode: x and the intermediate
+    silu(g) * u are rounded to OCP MXFP8 (ops.quantize_mxfp8's rule, blocks of
+    32 consecutive h and f) before they meet the weights. Under the same
+    conditions it runs moe_expert_mxfp4w_a8_kernel, which feeds both sets of
+    codes and scale bytes to v_mfma_scale_f32_32x32x64_f8f6f4 as they are: x
+    is quantised by one launch for gate and up, the intermediate in the
+    gate/up epilogue from the fp32 accumulators (never rounded to bf16);
+    every other case takes reference.moe_ffn_mxfp4w_a8. Any other act_quant
+    raises ValueError."""
+    if act_quant not in (None, "mxfp8"):
+        raise ValueError(f"moe_ffn_mxfp4w: act_quant must be None or 'mxfp8', got {act_quant!r}")
     if x.dim() != 2 or router_logits.dim() != 2 or router_logits.shape[0] != x.shape[0]:
         raise ValueError("moe_ffn_mxfp4w: x must be [T, h] and router_logits [T, E]")
     t, h = x.shape
@@ -907,12 +921,13 @@ def moe_ffn_mxfp4w(x: torch.Tensor, router_logits: torch.Tensor, c_gate: torch.T
     if not isinstance(top_k, int) or not 1 <= top_k <= n_experts:
         raise ValueError(f"moe_ffn_mxfp4w: top_k must be an int in [1, {n_experts}], got {top_k}")
     if use_native(x) and moe_ffn_native_shapes(h, f, n_experts, top_k):
-        return _c().moe_ffn_mxfp4w(x.contiguous(), router_logits.contiguous(),
-                                   c_gate.contiguous(), e_gate.contiguous(),
-                                   c_up.contiguous(), e_up.contiguous(),
-                                   c_down.contiguous(), e_down.contiguous(), top_k)
-    return reference.moe_ffn_mxfp4w(x, router_logits, c_gate, e_gate, c_up, e_up, c_down,
-                                    e_down, top_k)
+        op = _c().moe_ffn_mxfp4w if act_quant is None else _c().moe_ffn_mxfp4w_a8
+        return op(x.contiguous(), router_logits.contiguous(),
+                  c_gate.contiguous(), e_gate.contiguous(),
+                  c_up.contiguous(), e_up.contiguous(),
+                  c_down.contiguous(), e_down.contiguous(), top_k)
+    ref = reference.moe_ffn_mxfp4w if act_quant is None else reference.moe_ffn_mxfp4w_a8
+    return ref(x, router_logits, c_gate, e_gate, c_up, e_up, c_down, e_down, top_k)
 
 
 # ---------------------------------------------------------------------------

@@ -303,6 +303,30 @@ def moe_ffn_mxfp4w(x: torch.Tensor, router_logits: torch.Tensor, c_gate: torch.T
     return out.to(x.dtype)
 
 
+def moe_ffn_mxfp4w_a8(x: torch.Tensor, router_logits: torch.Tensor, c_gate: torch.Tensor,
+                      e_gate: torch.Tensor, c_up: torch.Tensor, e_up: torch.Tensor,
+                      c_down: torch.Tensor, e_down: torch.Tensor, top_k: int) -> torch.Tensor:
+    """moe_ffn_mxfp4w with both activations rounded to MXFP8 (quantize_mxfp8,
+    blocks of 32 consecutive inputs): x before gate and up, v = silu(g) * u
+    before down. The same routing, each projection a linear_mxfp4w_a8."""
+    logits = router_logits.float()
+    probs = torch.softmax(logits, dim=-1)
+    topi = torch.sort(logits, dim=-1, descending=True, stable=True).indices[:, :top_k]
+    topw = probs.gather(1, topi)
+    topw = topw / topw.sum(-1, keepdim=True)
+    out = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
+    for e in range(c_gate.shape[0]):
+        tok, slot = (topi == e).nonzero(as_tuple=True)
+        if tok.numel() == 0:
+            continue
+        xe = x[tok]
+        he = swiglu(linear_mxfp4w_a8(xe, c_gate[e], e_gate[e]),
+                    linear_mxfp4w_a8(xe, c_up[e], e_up[e]))
+        ye = linear_mxfp4w_a8(he, c_down[e], e_down[e]).float() * topw[tok, slot].unsqueeze(1)
+        out.index_add_(0, tok, ye)
+    return out.to(x.dtype)
+
+
 # ---------------------------------------------------------------------------
 # Cross-entropy over vocab (fp32 logits path)
 # ---------------------------------------------------------------------------

@@ -12,7 +12,7 @@ so the scheduler's FSM and lease machinery apply unchanged.
 Job config: {"model", "data": <fetch ref>, "results": <send ref>?,
              "max_new_tokens", "batch_size", "seq_len", "temperature",
              "top_k", "top_p"?, "sampler": "philox"?, "seed"?,
-             "num_batches", "kv_cache": "fp8"?, "weight_quant": "fp8" | "mxfp4" | "mxfp4_a8"?,
+             "num_batches", "kv_cache": "fp8"?, "weight_quant": "fp8" | "mxfp4" | "mxfp4_a8" | "mxfp4_experts_a8"?,
              "prefill_chunk": <int>?, "pad_token_id": <int>?,
              "eos_token_id": <int>?, "kv_layout": "paged"?, "kv_pages": <int>?}
 
@@ -31,7 +31,9 @@ MXFP4 instead (models/mxfp4_linear.py: e2m1 codes with one power-of-two scale
 per 32 inputs, 4.25 bits per weight). Either one quantises the experts of the
 MoE family the same way. "weight_quant": "mxfp4_a8" is "mxfp4" with the
 linears' activations rounded to MXFP8 on the way in (act_quant="mxfp8"; the
-experts stay weight-only MXFP4). Any other value is an error.
+experts stay weight-only MXFP4); "weight_quant": "mxfp4_experts_a8" is "mxfp4"
+with MXFP8 activations inside the expert FFN instead (the linears stay
+weight-only). Any other value is an error.
 
 "pad_token_id" makes every batch RAGGED: prompts are right-padded rows, a
 prompt's length is its row without the trailing run of that id (at least one
@@ -67,8 +69,8 @@ def prompt_lengths(prompts: torch.Tensor, pad_token_id: int) -> torch.Tensor:
 
 
 def weight_quant(cfg: dict):
-    """The job's "weight_quant": None, "fp8", "mxfp4" or "mxfp4_a8"; anything
-    else raises."""
+    """The job's "weight_quant": None, "fp8", "mxfp4", "mxfp4_a8" or
+    "mxfp4_experts_a8"; anything else raises."""
     from hypha_amd.models.fp8_linear import check_weight_quant
 
     check_weight_quant(cfg.get("weight_quant"))
@@ -115,8 +117,10 @@ def main() -> int:
     model.eval()
     if wq == "fp8":
         models.quantize_linears_fp8_(model)
-    elif wq in ("mxfp4", "mxfp4_a8"):
-        models.quantize_linears_mxfp4_(model, "mxfp8" if wq == "mxfp4_a8" else None)
+    elif wq in ("mxfp4", "mxfp4_a8", "mxfp4_experts_a8"):
+        models.quantize_linears_mxfp4_(
+            model, "mxfp8" if wq == "mxfp4_a8" else None,
+            expert_act_quant="mxfp8" if wq == "mxfp4_experts_a8" else None)
 
     batch_size =int(cfg.get("batch_size", 1))
     seq_len = int(cfg.get("seq_len", 64))

@@ -4,8 +4,8 @@ token count. Device events around `iters` forwards over 8 rotating inputs
 (so the routing varies), the two paths alternated `rounds` times; the median
 round and the spread are printed, one JSON line per T.
 
-  python tools/moe_ffn_bench.py [--iters 200] [--rounds 3] [--w-fp8 | --w-mxfp4]
-  rocprofv3 --kernel-trace --stats -- python tools/moe_ffn_bench.py --trace T [--w-fp8 | --w-mxfp4]
+  python tools/moe_ffn_bench.py [--iters 200] [--rounds 3] [--w-fp8 | --w-mxfp4 [--a-mxfp8]]
+  rocprofv3 --kernel-trace --stats -- python tools/moe_ffn_bench.py --trace T [--w-fp8 | --w-mxfp4 [--a-mxfp8]]
 
 --w-fp8 times three paths the same way: a copy of the module on weight-only
 fp8 experts (MoEMLP.quantize_experts_fp8_) through ops.moe_ffn_fp8w and
@@ -17,8 +17,12 @@ as the baseline for time.
 ops.linear_mxfp4w, and the fp8 and bf16 fused paths as baselines, all four
 alternated in one call.
 
+--a-mxfp8 (with --w-mxfp4) adds a second copy of the MXFP4 module with
+act_quant="mxfp8" (MXFP8 activations, ops.moe_ffn_mxfp4w(..., act_quant="mxfp8"))
+as a fifth path, alternated with the others.
+
 --trace T runs 40 fused forwards at T tokens (on the fp8 experts with --w-fp8,
-on the MXFP4 experts with --w-mxfp4)
+on the MXFP4 experts with --w-mxfp4, in their MXFP8 mode with --a-mxfp8)
 and prints the number of live experts of each input, from which the bytes the
 two streaming kernels had to read follow (gate/up: live * 2 * f * h * B, down:
 live * h * f * B, B = 2 bytes per bf16 weight, 1 per fp8 code, 17 / 32 per
@@ -81,7 +85,10 @@ def main():
     ap.add_argument("--trace", type=int, default=0)
     ap.add_argument("--w-fp8", action="store_true")
     ap.add_argument("--w-mxfp4", action="store_true")
+    ap.add_argument("--a-mxfp8", action="store_true")
     args = ap.parse_args()
+    if args.a_mxfp8 and not args.w_mxfp4:
+        ap.error("--a-mxfp8 needs --w-mxfp4")
     mlp = build()
     mlp8 = mlp4 = None
     if args.w_fp8 or (args.w_mxfp4 and not args.trace):
@@ -90,9 +97,12 @@ def main():
     if args.w_mxfp4:
         mlp4 = copy.deepcopy(mlp)
         mlp4.quantize_experts_mxfp4_()
+    if args.a_mxfp8:
+        mlp4a = copy.deepcopy(mlp4)  # the same codes, the other numerical mode
+        mlp4a.act_quant = "mxfp8"
     if args.trace:
         xs = inputs(args.trace)
-        run = mlp4 if args.w_mxfp4 else mlp8 if args.w_fp8 else mlp
+        run = mlp4a if args.a_mxfp8 else mlp4 if args.w_mxfp4 else mlp8 if args.w_fp8 else mlp
         with torch.no_grad():
             live = [len(set(mlp.router(x[0]).float().topk(2, -1).indices.reshape(-1).tolist()))
                     for x in xs]
@@ -110,6 +120,8 @@ def main():
     if args.w_mxfp4:
         paths = [("mxfp4_fused", mlp4, True), ("mxfp4_loop", mlp4, False),
                  ("fp8_fused", mlp8, True), ("bf16_fused", mlp, True)]
+    if args.a_mxfp8:
+        paths.insert(1, ("mxfp4_a8_fused", mlp4a, True))
     token_counts = (1, 2, 4, 8, 16, 32, 64, 128, 256, 512)
     if args.w_fp8 or args.w_mxfp4:  # the loops dequantise whole experts above 128 rows: look further
         token_counts += (1024, 2048, 4096)
