@@ -119,7 +119,7 @@ class GPT2ForCausalLM(nn.Module):
         logits = F.linear(x, self.wte.weight)  # tied head
         if labels is None:
             return logits
-        return ops.cross_entropy_loss(logits[:, :-1], labels[:, 1:])
+        return ops.cross_entropy_loss(logits, labels, shift=True)
 
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,

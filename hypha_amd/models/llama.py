@@ -229,7 +229,7 @@ class LlamaForCausalLM(nn.Module):
         if labels is None:
             return logits
         # next-token prediction: shift
-        loss = ops.cross_entropy_loss(logits[:, :-1], labels[:, 1:])
+        loss = ops.cross_entropy_loss(logits, labels, shift=True)
         return loss
 
 

@@ -516,7 +516,7 @@ class MoEForCausalLM(nn.Module):
         logits = self.lm_head(x)
         if labels is None:
             return logits
-        loss = ops.cross_entropy_loss(logits[:, :-1], labels[:, 1:])
+        loss = ops.cross_entropy_loss(logits, labels, shift=True)
         if self.training and aux_total is not None:
             loss = loss + aux_total.float()
         return loss

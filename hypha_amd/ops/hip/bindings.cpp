@@ -8,6 +8,10 @@
 void adamw_step_(torch::Tensor master, torch::Tensor param, torch::Tensor grad,
                  torch::Tensor m, torch::Tensor v, double lr, double beta1, double beta2,
                  double eps, double wd, long step);
+void adamw_step_scaled_(torch::Tensor master, torch::Tensor param, torch::Tensor grad,
+                        torch::Tensor m, torch::Tensor v, torch::Tensor grad_scale,
+                        double lr, double beta1, double beta2, double eps, double wd,
+                        long step);
 void nesterov_step_(torch::Tensor theta, torch::Tensor delta, torch::Tensor mom, double lr,
                     double mu);
 void extract_delta(torch::Tensor master, torch::Tensor theta0, torch::Tensor out);
@@ -178,9 +182,16 @@ torch::Tensor linear_mxfp4w(torch::Tensor x, torch::Tensor codes, torch::Tensor 
 torch::Tensor linear_mxfp4w_a8(torch::Tensor x, torch::Tensor codes, torch::Tensor scales,
                                long depth);
 std::tuple<torch::Tensor, torch::Tensor> quantize_mxfp8(torch::Tensor x);
+// linear_bwd.hip (bias-free linear backward, dw written into the grad buffer)
+std::tuple<torch::Tensor, torch::Tensor> linear_bwd(torch::Tensor dy, torch::Tensor x,
+                                                    torch::Tensor weight,
+                                                    std::optional<torch::Tensor> dw_out,
+                                                    bool accumulate, bool need_dx);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adamw_step_", &adamw_step_);
+  m.def("adamw_step_scaled_", &adamw_step_scaled_);
+  m.def("linear_bwd", &linear_bwd);
   m.def("nesterov_step_", &nesterov_step_);
   m.def("extract_delta", &extract_delta);
   m.def("adamw8_step_", &adamw8_step_);

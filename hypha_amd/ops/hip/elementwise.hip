@@ -16,11 +16,16 @@
 // param out (bf16x8). ~26 B/elem traffic.
 // ---------------------------------------------------------------------------
 
+// SCALED: the gradient is first multiplied by *grad_scale, a device scalar
+// (the clip coefficient), exactly as a separate bf16 pass would have done it:
+// coefficient rounded to bf16, product taken in fp32 and rounded to bf16.
+template <bool SCALED>
 __global__ void adamw_kernel(float* __restrict__ master, short* __restrict__ param,
                              const short* __restrict__ grad, float* __restrict__ m,
                              float* __restrict__ v, long long n, float lr, float beta1,
                              float beta2, float eps, float wd, float inv_bc1,
-                             float inv_bc2) {
+                             float inv_bc2, const float* __restrict__ grad_scale) {
+  const float gs = SCALED ? bf2f(f2bf(*grad_scale)) : 1.f;
   const long long stride = (long long)gridDim.x * blockDim.x * 8;
   for (long long base = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 8; base < n;
        base += stride) {
@@ -36,6 +41,7 @@ __global__ void adamw_kernel(float* __restrict__ master, short* __restrict__ par
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float g = bf2f(g8[j]);
+        if (SCALED) g = bf2f(f2bf(g * gs));
         float mm = j < 4 ? m0[j] : m1[j - 4];
         float vv = j < 4 ? v0[j] : v1[j - 4];
         float ww = j < 4 ? w0[j] : w1[j - 4];
@@ -57,6 +63,7 @@ __global__ void adamw_kernel(float* __restrict__ master, short* __restrict__ par
     } else {
       for (long long i = base; i < n; ++i) {
         float g = bf2f(grad[i]);
+        if (SCALED) g = bf2f(f2bf(g * gs));
         float mm = beta1 * m[i] + (1.f - beta1) * g;
         float vv = beta2 * v[i] + (1.f - beta2) * g * g;
         float denom = sqrtf(vv * inv_bc2) + eps;
@@ -70,9 +77,10 @@ __global__ void adamw_kernel(float* __restrict__ master, short* __restrict__ par
   }
 }
 
-void adamw_step_(torch::Tensor master, torch::Tensor param, torch::Tensor grad,
-                 torch::Tensor m, torch::Tensor v, double lr, double beta1, double beta2,
-                 double eps, double wd, long step) {
+static void adamw_launch(torch::Tensor& master, torch::Tensor& param, torch::Tensor& grad,
+                         torch::Tensor& m, torch::Tensor& v, double lr, double beta1,
+                         double beta2, double eps, double wd, long step,
+                         const float* grad_scale) {
   TORCH_CHECK(master.is_cuda() && master.dtype() == torch::kFloat32);
   TORCH_CHECK(param.dtype() == torch::kBFloat16 && grad.dtype() == torch::kBFloat16);
   long long n = master.numel();
@@ -80,11 +88,32 @@ void adamw_step_(torch::Tensor master, torch::Tensor param, torch::Tensor grad,
   float inv_bc1 = 1.f / (1.f - powf((float)beta1, (float)step));
   float inv_bc2 = 1.f / (1.f - powf((float)beta2, (float)step));
   hipStream_t stream = hypha_stream();
-  hipLaunchKernelGGL(adamw_kernel, dim3(elementwise_grid((n + 7) / 8)), dim3(256), 0,
-                     stream, master.data_ptr<float>(), (short*)param.data_ptr(),
+  auto kernel = grad_scale ? adamw_kernel<true> : adamw_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(elementwise_grid((n + 7) / 8)), dim3(256), 0, stream,
+                     master.data_ptr<float>(), (short*)param.data_ptr(),
                      (const short*)grad.data_ptr(), m.data_ptr<float>(),
                      v.data_ptr<float>(), n, (float)lr, (float)beta1, (float)beta2,
-                     (float)eps, (float)wd, inv_bc1, inv_bc2);
+                     (float)eps, (float)wd, inv_bc1, inv_bc2, grad_scale);
+}
+
+void adamw_step_(torch::Tensor master, torch::Tensor param, torch::Tensor grad,
+                 torch::Tensor m, torch::Tensor v, double lr, double beta1, double beta2,
+                 double eps, double wd, long step) {
+  adamw_launch(master, param, grad, m, v, lr, beta1, beta2, eps, wd, step, nullptr);
+}
+
+// adamw_step_ on gradients scaled by grad_scale (fp32, one element, on the
+// device; read by the kernel, so no host sync). grad itself is not written.
+void adamw_step_scaled_(torch::Tensor master, torch::Tensor param, torch::Tensor grad,
+                        torch::Tensor m, torch::Tensor v, torch::Tensor grad_scale,
+                        double lr, double beta1, double beta2, double eps, double wd,
+                        long step) {
+  TORCH_CHECK(grad_scale.is_cuda() && grad_scale.dtype() == torch::kFloat32 &&
+                  grad_scale.numel() == 1 &&
+                  grad_scale.get_device() == master.get_device(),
+              "adamw_step_scaled_: grad_scale must be one fp32 element on master's device");
+  adamw_launch(master, param, grad, m, v, lr, beta1, beta2, eps, wd, step,
+               grad_scale.data_ptr<float>());
 }
 
 // ---------------------------------------------------------------------------

@@ -21,6 +21,8 @@ The HIP extension ABI (hypha_amd._C):
   attn_prefill_paged(q, kpool, vpool, kscale?, vscale?, table_i32, pos, seq_lens_i32?) -> o
   kv_append_paged_(k, v, kpool, vpool, kscale?, vscale?, table_i32, pos_i64, lens_i32?)
   adamw_step_(master, param, grad, m, v, lr, b1, b2, eps, wd, step)
+  adamw_step_scaled_(master, param, grad, m, v, grad_scale_f32[1], lr, b1, b2, eps, wd, step)
+  linear_bwd(dy2d, x2d, weight, dw_out?, accumulate, need_dx) -> (dx?, dw)
   adamw8_step_(master, param, grad, m8, v8, m_scale, v_scale, ...)  # 8-bit state
   nesterov_step_(master, delta_bf16, momentum, lr, mu)
   extract_delta(master, theta0, out_bf16)
@@ -42,6 +44,8 @@ The HIP extension ABI (hypha_amd._C):
 
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import reference
@@ -52,6 +56,20 @@ def _c():
     from hypha_amd import _C
 
     return _C
+
+
+# HYPHA_STEP_ABLATE: perf-diagnosis bitmask for the training step (default 0).
+# Each bit puts back passes over memory that the step no longer makes, with
+# the same results, so both forms can be timed and compared in one build:
+STEP_ABLATE_CLIP = 1   # clip as a separate grad.mul_ pass in front of AdamW
+STEP_ABLATE_WGRAD = 2  # autograd's dw temporaries + grad adds, whole-buffer zero_grad
+STEP_ABLATE_LOSS = 4   # loss on sliced logits (copy forward, zeros + copy backward)
+
+
+def step_ablate() -> int:
+    """The HYPHA_STEP_ABLATE bitmask, read at call time (DiLoCoWorker reads it
+    once, when it is built)."""
+    return int(os.environ.get("HYPHA_STEP_ABLATE") or 0)
 
 
 # ---------------------------------------------------------------------------
@@ -990,6 +1008,66 @@ def philox_uniform(seed, step, n: int, device=None) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------
+# Bias-free linear whose weight gradient is written in place (training)
+# ---------------------------------------------------------------------------
+
+
+def wgrad_inplace_ok(weight: torch.Tensor) -> bool:
+    """True when _LinearWgradInplace writes weight's gradient into weight.grad:
+    the parameter is marked (`_wgrad_fresh` set, by FlatParams) and its grad
+    is a CUDA bf16 tensor of the weight's shape and dtype, contiguous and
+    16-byte aligned. FlatParams decides with the same test which ranges it no
+    longer zeroes."""
+    g = weight.grad
+    return (getattr(weight, "_wgrad_fresh", None) is not None
+            and g is not None and g.is_cuda and g.dtype == torch.bfloat16
+            and weight.dtype == torch.bfloat16 and g.shape == weight.shape
+            and g.is_contiguous() and g.data_ptr() % 16 == 0)
+
+
+class _LinearWgradInplace(torch.autograd.Function):
+    """y = x @ weight^T. Backward runs the two GEMMs of autograd's own linear
+    backward (_C.linear_bwd), but where wgrad_inplace_ok(weight) holds the
+    wgrad GEMM's output is weight.grad itself and autograd gets None for the
+    weight: no dw temporary and no grad += dw. `weight._wgrad_fresh` (True:
+    grad holds nothing to keep) makes the first write of a step overwrite
+    and any later one accumulate. Otherwise dw is returned as usual."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        ctx.save_for_backward(x, weight)
+        ctx.param = weight  # the Parameter object itself: its .grad and flag
+        return torch.nn.functional.linear(x, weight)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        need_dx, need_dw = ctx.needs_input_grad
+        n, k = weight.shape
+        dy2d = dy.reshape(-1, n)
+        if not need_dw:
+            return (dy2d @ weight).view(x.shape) if need_dx else None, None
+        x2d = x.reshape(-1, k)
+        param = ctx.param
+        if dy.dtype == weight.dtype and wgrad_inplace_ok(param):
+            dx, _ = _c().linear_bwd(dy2d, x2d, weight, param.grad,
+                                    not param._wgrad_fresh, need_dx)
+            param._wgrad_fresh = False
+            dw = None
+        else:
+            dx, dw = _c().linear_bwd(dy2d, x2d, weight, None, False, need_dx)
+        return dx.view(x.shape) if need_dx else None, dw
+
+
+def linear_wgrad_inplace(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """Bias-free linear for training under FlatParams (see _LinearWgradInplace);
+    a plain linear on the CPU."""
+    if use_native(x) and x.dtype == weight.dtype:
+        return _LinearWgradInplace.apply(x, weight)
+    return torch.nn.functional.linear(x, weight)
+
+
+# ---------------------------------------------------------------------------
 # Cross-entropy over vocab (memory-frugal: backward overwrites the logits)
 # ---------------------------------------------------------------------------
 
@@ -1010,8 +1088,29 @@ class _CrossEntropy(torch.autograd.Function):
         return dlogits, None
 
 
-def cross_entropy_loss(logits: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
-    """logits [..., V], targets [...] int64 with -100 = ignore. Mean loss."""
+def cross_entropy_loss(logits: torch.Tensor, targets: torch.Tensor,
+                       shift: bool = False) -> torch.Tensor:
+    """logits [..., V], targets [...] int64 with -100 = ignore. Mean loss.
+
+    shift=True is next-token prediction on unsliced operands: logits
+    [B, S, V], targets = labels [B, S], the loss of logits[:, :-1] against
+    labels[:, 1:]. The native path does not slice (a sliced logits tensor is
+    not contiguous: its reshape copies all of it, and autograd's slice
+    backward allocates a zeroed tensor of the full size and copies dlogits
+    into it). It runs the kernels on the whole [B*S, V] view against targets
+    shifted left by one with -100 in the last column: ignored rows add nothing
+    to the loss and their gradient rows are written as zeros, so every
+    gradient is the same bits. The CPU path slices as the callers used to."""
+    if shift:
+        if logits.dim() != 3 or targets.shape != logits.shape[:2]:
+            raise ValueError("cross_entropy_loss: shift=True needs logits [B, S, V] "
+                             "and targets [B, S]")
+        if (use_native(logits) and logits.is_contiguous()
+                and not step_ablate() & STEP_ABLATE_LOSS):
+            t = torch.full_like(targets, -100)
+            t[:, :-1] = targets[:, 1:]
+            return _CrossEntropy.apply(logits.view(-1, logits.shape[-1]), t.view(-1))
+        logits, targets = logits[:, :-1], targets[:, 1:]
     v = logits.shape[-1]
     logits2d = logits.reshape(-1, v)
     t = targets.reshape(-1)
@@ -1026,10 +1125,23 @@ def cross_entropy_loss(logits: torch.Tensor, targets: torch.Tensor) -> torch.Ten
 
 
 @torch.no_grad()
-def fused_adamw(master, param, grad, exp_avg, exp_avg_sq, *, lr, beta1, beta2, eps, weight_decay, step):
+def fused_adamw(master, param, grad, exp_avg, exp_avg_sq, *, lr, beta1, beta2, eps, weight_decay, step,
+                grad_scale=None):
+    """grad_scale (a 1-element tensor on grad's device, e.g. the clip
+    coefficient): the update runs on grad * grad_scale as a separate pass in
+    grad's dtype would have produced it (grad_scale rounded to grad's dtype,
+    the product rounded to it), but grad is read once and not written. On the
+    GPU the kernel reads the scalar itself: no host sync."""
     if use_native(master):
-        _c().adamw_step_(master, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step)
+        if grad_scale is None:
+            _c().adamw_step_(master, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step)
+        else:
+            _c().adamw_step_scaled_(master, param, grad, exp_avg, exp_avg_sq,
+                                    grad_scale.reshape(1).float(), lr, beta1, beta2, eps,
+                                    weight_decay, step)
     else:
+        if grad_scale is not None:
+            grad = grad * grad_scale.to(grad.dtype)
         reference.adamw_step(
             master, param, grad, exp_avg, exp_avg_sq,
             lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, step=step,

@@ -122,9 +122,53 @@ class FlatParams:
             self.exp_avg_sq = torch.zeros_like(self.master)
         self.theta0 = self.master.clone()  # global weights at round start
         self.outer_momentum = torch.zeros_like(self.master)
+        # parameters whose gradient the wgrad GEMM writes in place
+        # (mark_wgrad_inplace), and the views of flat_grad left to zero
+        self.inplace_params: list[nn.Parameter] = []
+        self._zero_views = [self.flat_grad]
+
+    def mark_wgrad_inplace(self, weights) -> int:
+        """`weights`: parameters of modules that run ops' in-place wgrad linear.
+        Those whose grad view qualifies (ops.interface.wgrad_inplace_ok) are
+        overwritten by the first wgrad GEMM of every step, so zero_grad skips
+        their ranges: it zeroes only what lies between them (embedding, norm
+        weights, anything not marked), adjacent ranges merged. Returns how
+        many were taken."""
+        chosen = {id(w) for w in weights}
+        self.inplace_params = []
+        gaps, start, offset = [], 0, 0
+        for p in self.params:
+            n = p.numel()
+            if id(p) in chosen:
+                p._wgrad_fresh = True
+                if ops.interface.wgrad_inplace_ok(p):
+                    self.inplace_params.append(p)
+                    if offset > start:
+                        gaps.append((start, offset))
+                    start = offset + n
+                else:
+                    del p._wgrad_fresh
+            offset += n
+        if offset > start:
+            gaps.append((start, offset))
+        self._zero_views = [self.flat_grad[a:b] for a, b in gaps]
+        return len(self.inplace_params)
 
     def zero_grad(self) -> None:
-        self.flat_grad.zero_()
+        if len(self._zero_views) == 1:
+            self._zero_views[0].zero_()
+        elif self._zero_views:
+            torch._foreach_zero_(self._zero_views)  # one launch for all ranges
+        for p in self.inplace_params:
+            p._wgrad_fresh = True  # nothing to keep: the next write overwrites
+
+    def zero_unwritten_grads(self) -> None:
+        """An in-place parameter that no backward wrote this step (an unused
+        layer, a router that saw no token) still holds the previous step's
+        gradient: zero it before anything reads the gradients."""
+        for p in self.inplace_params:
+            if p._wgrad_fresh:
+                p.grad.zero_()
 
     def grad_norm(self) -> torch.Tensor:
         # fp32 accumulation without materializing an fp32 copy of the grads
@@ -133,6 +177,44 @@ class FlatParams:
 
             return _C.grad_norm_sq(self.flat_grad).sqrt_()
         return torch.linalg.vector_norm(self.flat_grad, dtype=torch.float32)
+
+
+class WgradInplaceLinear(nn.Linear):
+    """A bias-free nn.Linear whose backward writes the weight gradient
+    straight into `weight.grad` (ops.interface._LinearWgradInplace). Takes
+    over the original module's Parameter: state-dict keys, the FlatParams
+    order and the checkpoint layout are unchanged."""
+
+    @classmethod
+    def from_linear(cls, lin: nn.Linear) -> "WgradInplaceLinear":
+        m = cls.__new__(cls)
+        nn.Module.__init__(m)
+        m.in_features, m.out_features = lin.in_features, lin.out_features
+        m.weight = lin.weight
+        m.register_parameter("bias", None)
+        return m
+
+    def forward(self, x):
+        return ops.interface.linear_wgrad_inplace(x, self.weight)
+
+
+def convert_linears_to_wgrad_inplace(model: nn.Module) -> list[nn.Parameter]:
+    """Swap, in place, every plain bias-free bf16 nn.Linear for
+    WgradInplaceLinear and return their weights. A weight that another
+    module owns too (tied) stays with autograd: its other gradient arrives
+    through an add, which an overwriting GEMM would lose."""
+    uses: dict[int, int] = {}
+    for _, p in model.named_parameters(remove_duplicate=False):
+        uses[id(p)] = uses.get(id(p), 0) + 1
+    weights = []
+    for parent in model.modules():
+        for name, child in list(parent.named_children()):
+            if (type(child) is nn.Linear and child.bias is None
+                    and child.weight.dtype == torch.bfloat16
+                    and child.weight.requires_grad and uses[id(child.weight)] == 1):
+                setattr(parent, name, WgradInplaceLinear.from_linear(child))
+                weights.append(child.weight)
+    return weights
 
 
 class DiLoCoWorker:
@@ -163,6 +245,13 @@ class DiLoCoWorker:
             if buf.dtype in (torch.bfloat16, torch.float16):
                 buf.data = buf.data.float()
         self.fp = FlatParams(model, device, work_dtype, state_bits=cfg.inner.state_bits)
+        # HYPHA_STEP_ABLATE (ops/interface.py) puts the step's former passes back
+        self._ablate = ops.interface.step_ablate()
+        if (ops.use_native(self.fp.flat)
+                and not self._ablate & ops.interface.STEP_ABLATE_WGRAD):
+            # wgrad GEMMs write into flat_grad: no dw temporaries, no grad
+            # adds, and zero_grad shrinks to what lies between those weights
+            self.fp.mark_wgrad_inplace(convert_linears_to_wgrad_inplace(model))
         # make every rank start from identical weights (rank0's init wins);
         # expert-parallel shards (the tail past sync_numel) stay rank-local
         if self.comm.is_distributed:
@@ -201,11 +290,18 @@ class DiLoCoWorker:
         self.inner_step_count += 1
         self.steps_in_round += 1
         c = self.cfg.inner
+        self.fp.zero_unwritten_grads()
+        clip_coef = None
         if self.cfg.grad_clip > 0:
             gnorm = self.fp.grad_norm()
-            # clamp to 1 and always scale: no host sync, one fused mul
+            # clamp to 1 and always scale: no host sync
             clip_coef = (self.cfg.grad_clip / (gnorm + 1e-6)).clamp_(max=1.0)
-            self.fp.flat_grad.mul_(clip_coef.to(self.fp.flat_grad.dtype))
+            if (self.fp.state_bits == 8
+                    or self._ablate & ops.interface.STEP_ABLATE_CLIP):
+                # a pass of its own over the gradients; the fp32-state AdamW
+                # applies the coefficient as it loads them instead
+                self.fp.flat_grad.mul_(clip_coef.to(self.fp.flat_grad.dtype))
+                clip_coef = None
         if self.fp.state_bits == 8:
             from hypha_amd import _C
 
@@ -228,6 +324,7 @@ class DiLoCoWorker:
                 eps=c.eps,
                 weight_decay=c.weight_decay,
                 step=self.inner_step_count,
+                grad_scale=clip_coef,
             )
         self.fp.zero_grad()
 
